@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — the driver's benchmark of mpi_perf's hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]          (N = 1)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N = 1)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints its line: the
+headline and what it needs (at N >= 2 the rounds' validation and the push
+tuning).  Everything else described below — the CPU baseline, the in-process
+counter passes behind `roofline.traffic`, and all that runs "after the timed
+steps" — runs with --full only.  --dump-outputs DIR writes what the last
+timed step left in the receiving buffer (N = 1: dst; N >= 2: each rank's rx)
+as DIR/<name>.npy, float32, one element per byte — a fixed seeded sample of
+blocks when the buffer is large — with the checksum of the whole buffer
+beside it; the inputs are seeded patterns, the same on every run.
 
 A "step" is one run of the reference's loop (mpi_perf.c:474-569: barrier ->
 `iters` x transfer -> barrier) over one batch of synthetic bytes:
@@ -429,6 +439,8 @@ def counters_skip_reason(args) -> str | None:
     """None when the in-process counters may run; else why not.  A process
     that rocprofv3 already profiles has its own rocprofiler tool (and
     dispatch counting serialises kernels): no second one is added."""
+    if not args.full:
+        return "not sampled: a plain run (the counter passes run with --full)"
     if args.no_counters:
         return "--no-counters"
     k = under_profiler()
@@ -1271,12 +1283,14 @@ def pair_latency(mpx, torch, dist, c, rounds, rank, world, tx, rx, errs) -> dict
 
 
 def pairs_bench(mpx, torch, dist, engine, rank, world, dev, nbytes, iters, steps, warmup, barrier_sync,
-                latency=True, tune=True, pull=False, prof=None, count: bool = False) -> dict:
+                latency=True, tune=True, pull=False, prof=None, count: bool = False, dump=None) -> dict:
     """All-pairs rounds on `engine` (one process per GPU, IPC-mapped peers;
     pull: the engine's MPX_XFER_PULL form, validation and steps alike).
     Every round's payloads are validated once (check mode, seeded per-rank
     patterns) before anything is timed.  prof (mpx/counters.py, registered):
-    the steps' link / DRAM bytes are counted after them.  Returns a dict;
+    the steps' link / DRAM bytes are counted after them.  dump(c, rx, nbytes),
+    if given, is called right after the timed steps, while rx holds what the
+    last of them received (--dump-outputs).  Returns a dict;
     "error" is set (on every rank) if any rank failed."""
     rounds = all_pairs_rounds(world)
     out = {}
@@ -1432,6 +1446,8 @@ def pairs_bench(mpx, torch, dist, engine, rank, world, dev, nbytes, iters, steps
         c.close()
         dist.barrier()
         return {"error": err}
+    if dump is not None:
+        dump(c, rx, nbytes)
     tt = torch.tensor([elapsed], dtype=torch.float64)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     out["elapsed"] = float(tt[0])
@@ -1515,13 +1531,14 @@ def pairs_bench(mpx, torch, dist, engine, rank, world, dev, nbytes, iters, steps
 
 
 def pairs_with_fallback(mpx, torch, dist, engine, rank, world, dev, nbytes, iters, steps, warmup, barrier_sync,
-                        extras: dict, latency: bool = True, prof=None, count: bool = False) -> tuple[dict, str]:
+                        extras: dict, latency: bool = True, prof=None, count: bool = False,
+                        dump=None) -> tuple[dict, str]:
     """pairs_bench on `engine`; if the kernel engine fails (payload
     validation, or a device timeout on any rank in validation or in the timed
     steps), measure the SDMA engine instead and say so: an explicit, labelled
     fallback, never a silent one."""
     res = pairs_bench(mpx, torch, dist, engine, rank, world, dev, nbytes, iters, steps, warmup, barrier_sync,
-                      latency=latency, prof=prof, count=count)
+                      latency=latency, prof=prof, count=count, dump=dump)
     engine_used = engine
     if res.get("error") and engine == "kernel":
         extras["kernel_engine_error"] = res["error"]
@@ -1529,7 +1546,7 @@ def pairs_with_fallback(mpx, torch, dist, engine, rank, world, dev, nbytes, iter
         # own buffers, so it is the last resort when IPC itself failed
         for fb_engine in ("sdma", "rccl"):
             fb = pairs_bench(mpx, torch, dist, fb_engine, rank, world, dev, nbytes, iters, steps, warmup,
-                             barrier_sync, latency=latency)
+                             barrier_sync, latency=latency, dump=dump)
             if not fb.get("error"):
                 res, engine_used = fb, f"{fb_engine} (fallback: kernel engine failed, extras.kernel_engine_error)"
                 break
@@ -1612,6 +1629,40 @@ def emit(fd: int, line: dict) -> None:
     os.write(fd, (json.dumps(line) + "\n").encode())
 
 
+# --dump-outputs: every file is float32, one element per output byte; all
+# files of one run together stay under DUMP_BUDGET_BYTES on disk
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_BLOCK, DUMP_SEED = 4096, 0x6D7078
+
+
+def dump_offsets(nbytes: int, max_elems: int) -> list[tuple[int, int]]:
+    """(offset, length) pieces of an nbytes output that --dump-outputs
+    writes: all of it when it fits in max_elems, else its first and last
+    DUMP_BLOCK bytes and DUMP_BLOCK-sized blocks at offsets drawn once from
+    a fixed seed (the same pieces on every run with the same arguments)."""
+    if nbytes <= max_elems:
+        return [(0, nbytes)]
+    import random
+    nblocks = max(max_elems // DUMP_BLOCK, 2)
+    inner = random.Random(DUMP_SEED).sample(range(1, (nbytes - DUMP_BLOCK) // DUMP_BLOCK), nblocks - 2)
+    offsets = [0] + [b * DUMP_BLOCK for b in sorted(inner)] + [nbytes - DUMP_BLOCK]
+    return [(off, DUMP_BLOCK) for off in offsets]
+
+
+def dump_output(c, buf, nbytes: int, directory: str, name: str, max_elems: int) -> None:
+    """Write what a caller of the timed path receives in `buf` (the bytes
+    the last timed step left there) as directory/name.npy, float32, one
+    element per byte (dump_offsets' pieces, in order), and the checksum of
+    all nbytes as directory/name_checksum.npy, float64 [high 32 bits, low 32
+    bits]: a sampled output still answers for every byte."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    parts = [np.frombuffer(c.read(buf, n, off), dtype=np.uint8) for off, n in dump_offsets(nbytes, max_elems)]
+    np.save(os.path.join(directory, name + ".npy"), np.concatenate(parts).astype(np.float32))
+    s = c.checksum(buf, nbytes)
+    np.save(os.path.join(directory, name + "_checksum.npy"), np.array([s >> 32, s & 0xFFFFFFFF], dtype=np.float64))
+
+
 def main() -> None:
     out_fd = quiet_stdout()
     ap = argparse.ArgumentParser()
@@ -1624,7 +1675,19 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-counters", action="store_true", help="no in-process hardware counters (mpx/counters.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline (the compiled reference), the in-process counter "
+                         "passes and every extra after the timed steps (sweeps, sustained rate, latency, comparison "
+                         "engines); without it a run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left in the receiving buffer as "
+                         "DIR/<name>.npy (float32, one element per byte; a fixed seeded sample of a large buffer) "
+                         "and its checksum as DIR/<name>_checksum.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only: --no-cpu-baseline,
+        # --no-extras and --no-counters narrow a --full run, here they all hold
+        args.no_cpu_baseline = args.no_extras = args.no_counters = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1755,6 +1818,8 @@ def main() -> None:
         barrier_sync()
         elapsed = time.perf_counter() - t0
         assert c.checksum(dst, nbytes) == c.checksum(src, nbytes), "copy output differs from its input"
+        if args.dump_outputs:
+            dump_output(c, dst, nbytes, args.dump_outputs, "dst", DUMP_BUDGET_BYTES // 4)
         total = nbytes * iters * args.steps
         per_launch = dev_s / max(launches, 1)
         algo = 2 * nbytes   # read B + write B per launch
@@ -1801,11 +1866,17 @@ def main() -> None:
     else:
         workload = "all_pairs_rounds_unidir"
         metric_unit = "GB/s"
+        dump = None
+        if args.dump_outputs:
+            # every rank writes what it received (G0 ranks the payload, G1
+            # ranks the 1-byte ack in front of what earlier rounds left)
+            def dump(c, rx, n):
+                dump_output(c, rx, n, args.dump_outputs, f"rx_rank{rank}", DUMP_BUDGET_BYTES // 4 // world)
         # --no-extras: nothing after the timed steps (profiling runs select
         # the timed launches as the last ones)
         res, engine_used = pairs_with_fallback(mpx, torch, pdist, args.engine, rank, world, dev, nbytes, iters,
                                                args.steps, args.warmup, barrier_sync, extras,
-                                               latency=not args.no_extras, prof=prof, count=count)
+                                               latency=not args.no_extras, prof=prof, count=count, dump=dump)
         elapsed, total = res["elapsed"], res["total"]
         achieved = res["per_pair_GBps"]
         roof = dict(bound="xgmi", achieved=round(achieved, 2), peak=XGMI_LINK_PEAK_GBPS, unit="GB/s",

@@ -102,6 +102,10 @@ class FakeMpx:
         def checksum(self, b, n):
             return (self.filled * 31 + n) & 0xFFFFFFFFFFFFFFFF     # a function of this rank's tx
 
+        def read(self, b, n, offset=0):
+            FakeMpx.log.append(["read", offset, n])
+            return bytes((offset + i + rank) & 0xFF for i in range(n))     # position and rank, nothing else
+
         def import_rank(self, r, desc):
             if scenario in ("import_fails", "all_fail") and rank == 1:
                 raise FakeError(f"cannot map rank {r}")

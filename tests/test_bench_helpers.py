@@ -166,3 +166,38 @@ def test_reference_legs_share_one_time_budget(monkeypatch):
     r = bench.run_reference(2, 1, ["-u", "1", "-b", "64", "-i", "5", "-r", "2"], 60)
     assert r["rc"] is None and "budget is spent" in r["stderr"] and r["times"] == [], r
     assert bench.cpu_baseline_pingpong()["GBps_4MiB"] is None
+
+
+def test_dump_offsets_cover_a_small_output_and_sample_a_large_one():
+    """--dump-outputs: an output that fits is written whole; a larger one as
+    its first and last block and seeded blocks between them — in bounds,
+    without overlap, within the element budget, the same on every call."""
+    assert bench.dump_offsets(1000, 4096) == [(0, 1000)]
+    assert bench.dump_offsets(4096, 4096) == [(0, 4096)]
+    for n, cap in ((1 << 30, bench.DUMP_BUDGET_BYTES // 4), ((1 << 20) + 4099, 65536), (8193, 8192)):
+        p = bench.dump_offsets(n, cap)
+        assert p == bench.dump_offsets(n, cap)
+        assert p[0] == (0, bench.DUMP_BLOCK) and p[-1] == (n - bench.DUMP_BLOCK, bench.DUMP_BLOCK)
+        assert sum(m for _, m in p) <= cap and len(p) == cap // bench.DUMP_BLOCK
+        assert all(a + m <= b for (a, m), (b, _) in zip(p, p[1:]))
+
+
+def test_dump_output_writes_float32_bytes_and_the_whole_checksum(tmp_path):
+    import numpy as np
+
+    data = bytes(range(256)) * 64          # 16 KiB
+
+    class C:
+        def read(self, buf, n, off=0):
+            return data[off:off + n]
+
+        def checksum(self, buf, n):
+            return 0x1234567890ABCDEF
+
+    bench.dump_output(C(), None, len(data), str(tmp_path / "d"), "dst", 8192)
+    a = np.load(tmp_path / "d" / "dst.npy")
+    assert a.dtype == np.float32 and a.shape == (8192,)
+    assert (a[:4096] == np.frombuffer(data[:4096], np.uint8)).all()
+    assert (a[4096:] == np.frombuffer(data[-4096:], np.uint8)).all()
+    s = np.load(tmp_path / "d" / "dst_checksum.npy")
+    assert s.dtype == np.float64 and (int(s[0]) << 32) | int(s[1]) == 0x1234567890ABCDEF

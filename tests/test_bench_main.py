@@ -13,7 +13,7 @@ KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "
         "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "extras"}
 
 
-def run(scenario, world=2, extra_env=None):
+def run(scenario, world=2, extra_env=None, args=("--full",)):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -23,7 +23,7 @@ def run(scenario, world=2, extra_env=None):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", **(extra_env or {}))
         ps.append(subprocess.Popen([sys.executable, os.path.join(HERE, "bench_main_worker.py"), scenario, "--gpus",
-                                    str(world), "--steps", "3", "--warmup", "1"], stdout=subprocess.PIPE,
+                                    str(world), "--steps", "3", "--warmup", "1", *args], stdout=subprocess.PIPE,
                                    stderr=subprocess.PIPE, text=True, env=env))
     outs = [p.communicate(timeout=120) for p in ps]
     return [p.returncode for p in ps], outs
@@ -83,6 +83,33 @@ def test_one_json_line_with_the_contract_keys():
     assert d["extras"]["hbv3_rounds_unidir"]["phases_us_median"]["g1"]["kernel_s"] == 1.0
     assert d["config"]["barrier"].startswith("node-local spin barrier") and d["config"]["launch"].startswith("armed")
     assert d["roofline"]["device_clock"].startswith("kernel-span (armed")
+
+
+def test_plain_run_is_the_headline_only(tmp_path):
+    """Without --full: the rounds validated, the push tuned, the steps timed
+    and the line printed — no reference leg, no counter pass, nothing after
+    the timed steps; the line keeps every key.  --dump-outputs: every rank
+    writes what it received (the stand-in's bytes: position + rank) and the
+    checksum of all of it."""
+    import numpy as np
+    rcs, outs = run("ok", args=("--dump-outputs", str(tmp_path)))
+    assert rcs == [0, 0], [o[1][-600:] for o in outs]
+    d = lines(outs[0][0])[0]
+    assert KEYS <= set(d) and d["value"] > 0 and d["steps"] == 3 and d["ms_per_step"] > 0
+    assert d["config"]["engine"] == "kernel" and d["config"]["validated_rounds"] == 1
+    assert d["cpu_baseline"] is None
+    assert d["roofline"]["traffic"] is None and "--full" in d["roofline"]["traffic_source"]
+    e = d["extras"]
+    assert not {"counters", "round0_sweep", "pingpong_8B_half_rtt_us", "hbv3_rounds_unidir", "sdma_aggregate_GBps",
+                "rccl_aggregate_GBps", "unidir_64MiB_per_pair_GBps", "push_vs_pull"} & set(e), sorted(e)
+    assert e["per_pair_unidir_GBps"] > 0 and e["pairs_covered"] == 1
+    assert sorted(os.listdir(tmp_path)) == ["rx_rank0.npy", "rx_rank0_checksum.npy", "rx_rank1.npy",
+                                            "rx_rank1_checksum.npy"]
+    for r in range(2):
+        a = np.load(tmp_path / f"rx_rank{r}.npy")
+        assert a.dtype == np.float32 and a.shape == (4 << 20,)         # 4 MiB fits two ranks' share: written whole
+        assert (a[:512] == (np.arange(512) + r) % 256).all()
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64e6
 
 
 def test_exit_path_with_and_without_a_profiler():

@@ -9,8 +9,8 @@
 # too (no GPU step runs after a fault or a hang).  Steps:
 #   smoke            __graft_entry__.smoke()
 #   pytest[:files]   the -m gpu suite (or the given test files, comma-separated)
-#   bench1           bench.py at N = 1 (defaults)
-#   rehearseN        bench.py at N ranks, every rank on GPU 0 (N = 2, 4, 8)
+#   bench1           bench.py --full at N = 1 (defaults)
+#   rehearseN        bench.py --full at N ranks, every rank on GPU 0 (N = 2, 4, 8)
 #   kt               rocprofv3 --kernel-trace --stats of the N = 1 bench
 #   pmc              rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the N = 1 bench
 #   stall            tools/exit_stall_repro: fenced vs barrier stream teardown cycles
@@ -51,7 +51,7 @@ step_ok() {  # name rc
 rehearse() {
     local n=$1 t0=$SECONDS
     MPX_BENCH_ONE_GPU=1 timeout -k 10 600 python3 -u -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-        --master-addr 127.0.0.1 --master-port $((29520 + n + RANDOM % 200)) bench.py --gpus $n \
+        --master-addr 127.0.0.1 --master-port $((29520 + n + RANDOM % 200)) bench.py --gpus $n --full \
         > $O/bench_n$n.json 2> $O/bench_n$n.err
     local rc=$?
     echo "rehearse$n: $((SECONDS - t0)) s"
@@ -189,7 +189,7 @@ for s in "$@"; do
         timeout -k 10 900 python3 -u -m pytest ${files//,/ } -m gpu -x -v --timeout 120 --timeout-method thread > $O/pytest_sel.log 2>&1
         rc=$?; tail -3 $O/pytest_sel.log; step_ok "$s" $rc ;;
     bench1)
-        timeout -k 10 400 python3 -u bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+        timeout -k 10 400 python3 -u bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
         step_ok bench1 $? ;;
     rehearse2) rehearse 2 ;;
     rehearse4) rehearse 4 ;;
@@ -260,7 +260,7 @@ for s in "$@"; do
         step_ok "node multi-GPU suite" $?
         for n in 2 4 8; do
             MPX_BENCH_ONE_GPU=$one timeout -k 10 900 python3 -u -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-                --master-addr 127.0.0.1 --master-port $((29700 + n)) bench.py --gpus $n \
+                --master-addr 127.0.0.1 --master-port $((29700 + n)) bench.py --gpus $n --full \
                 > $O/bench_node_n$n.json 2> $O/bench_node_n$n.err
             step_ok "node bench n$n" $?
         done
