@@ -319,6 +319,101 @@ typedef struct mpx_phases {
 } mpx_phases;
 int mpx_last_phases(mpx_ctx *ctx, int rank, mpx_phases *out);
 
+/* ---- per-iteration latency distribution (kernel engine) ------------------- */
+/* Every figure above is a mean: a call's time over its iterations (an
+   MPI_Wtime pair per message would cost the reference as much as the
+   message, mpi_perf.c:501,532-533).  Here the whole loop runs inside one
+   kernel, whose workgroup 0 can read its clock (s_memrealtime, the clock of
+   mpx_phases: 100 MHz, 10 ns ticks) once per iteration.  While a rank's
+   recorder is enabled, every ping-pong and unidir call of that rank records
+   the time of each of its iterations: t[0] is the instant first_iter_s
+   counts from, t[i+1] the end of iteration i on workgroup 0, and
+   d = t[i+1] - t[i] goes into min / max / sum, a log-linear histogram and
+   (the first raw_cap iterations of each call) a raw trace of the stamps.
+   The statistics accumulate over calls until mpx_lat_reset.
+     - Kernel engine only: the SDMA and RCCL engines refuse mpx_lat_enable
+       (MPX_ERR_UNSUPPORTED).
+     - A non-blocking call on an enabled rank runs untraced, exactly as on a
+       rank that is not enabled (its iterations have no blocking step).
+     - mpx_lat_enable / _disable / _reset / _get / _raw on a rank that holds
+       an armed call return MPX_ERR_STATE (enable before mpx_xfer_arm to
+       trace the armed call); _get and _raw on a rank that is not enabled
+       return MPX_ERR_STATE.
+     - The recorder never makes a transfer fail.  A call that fails (timeout,
+       check) leaves the recorder's contents undefined until mpx_lat_reset.
+     - With the recorder off no call reads the clock more often than before:
+       traced calls run kernels of their own (k_xfer_lat, k_xfer_pull_lat).
+   The ABI version is unchanged: callers detect the feature by symbol. */
+#define MPX_LAT_BUCKETS 464
+#define MPX_LAT_RAW_MAX (1 << 22)  /* largest raw_cap mpx_lat_enable accepts  */
+typedef struct mpx_lat {
+    uint64_t count;        /* iterations accumulated since enable / reset      */
+    uint64_t calls;        /* traced calls accumulated                          */
+    uint64_t min_ticks, max_ticks, sum_ticks;
+    uint64_t max_iter;     /* iteration (within its call) of the first maximum  */
+    uint64_t last_iters;   /* iterations of the last traced call                */
+    double   tick_s;       /* 1e-8                                              */
+    uint32_t hist[MPX_LAT_BUCKETS];
+} mpx_lat;
+/* raw_cap in [0, MPX_LAT_RAW_MAX]: stamps kept per call beyond t[0]; resets */
+int mpx_lat_enable(mpx_ctx *ctx, int rank, int raw_cap);
+int mpx_lat_disable(mpx_ctx *ctx, int rank);
+int mpx_lat_reset(mpx_ctx *ctx, int rank);
+int mpx_lat_get(mpx_ctx *ctx, int rank, mpx_lat *out);
+/* the last traced call's stamps t[0 .. min(iters, raw_cap)], at most `cap` of
+   them, into stamps[]; *n = how many were written (0 before any traced call) */
+int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
+
+/* The histogram's buckets, one definition for host and device.  Log-linear:
+   v < 32 ticks is its own bucket (exact below 320 ns); above, each power of
+   two [2^e, 2^(e+1)) splits into 16 equal buckets (<= 1/16 relative);
+   v >= 2^32 ticks (43 s, beyond any deadline) clamps to the last bucket. */
+#if defined(__HIPCC__)
+#define MPX_HD __host__ __device__
+#else
+#define MPX_HD
+#endif
+static inline MPX_HD int mpx_lat_bucket(uint64_t v)
+{
+    int e = 5;
+    if (v < 32) return (int)v;
+    if (v >> 32) return MPX_LAT_BUCKETS - 1;
+#if defined(__GNUC__) || defined(__clang__)
+    e = 63 - __builtin_clzll((unsigned long long)v);
+#else
+    while (v >> (e + 1)) ++e;
+#endif
+    return 32 + (e - 5) * 16 + (int)((v >> (e - 4)) & 15);
+}
+/* smallest value of bucket b (b = MPX_LAT_BUCKETS gives the clamp, 2^32) */
+static inline MPX_HD uint64_t mpx_lat_bucket_floor(int b)
+{
+    if (b < 32) return b < 0 ? 0 : (uint64_t)b;
+    return (uint64_t)(16 + (b - 32) % 16) << ((b - 32) / 16 + 1);
+}
+/* q in [0, 1] -> ticks: the floor of the first bucket whose cumulative count
+   reaches ceil(q * count), clamped to [min_ticks, max_ticks]; 0 if empty */
+static inline uint64_t mpx_lat_quantile(const mpx_lat *l, double q)
+{
+    uint64_t want, cum = 0, v;
+    double x;
+    int b;
+    if (!l || l->count == 0) return 0;
+    if (q < 0) q = 0;
+    if (q > 1) q = 1;
+    x = q * (double)l->count;
+    want = (uint64_t)x;
+    if ((double)want < x) ++want;
+    for (b = 0; b < MPX_LAT_BUCKETS - 1; ++b) {
+        cum += l->hist[b];
+        if (cum >= want) break;
+    }
+    v = mpx_lat_bucket_floor(b);
+    if (v < l->min_ticks) v = l->min_ticks;
+    if (v > l->max_ticks) v = l->max_ticks;
+    return v;
+}
+
 /* MPI_Barrier analogue (mpi_perf.c:499,557,579) for the threads of ONE
    process: blocks until `nthreads` callers have entered with the same ctx.
    Multi-process hosts use their own barrier. */

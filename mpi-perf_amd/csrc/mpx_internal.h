@@ -142,6 +142,22 @@ inline int ring_slots(unsigned long long ring_bytes, long long len) {
 }
 __host__ __device__ inline int ring_slot(int j, int iters, int slots) { return (iters - 1 - j) % slots; }
 
+// A rank's latency recorder (mpx_lat_enable), in that rank's device memory.
+// Written by lane 0 of workgroup 0 of the rank's traced calls (k_xfer_lat,
+// k_xfer_pull_lat) — a rank runs one call at a time — and by the host only
+// between calls, on the rank's stream (reset).  The block is allocated with
+// room for raw_cap + 1 stamps behind it, and raw_cap stands in the block
+// itself: the kernel bounds its raw stores by the very word the allocation
+// was sized with.
+struct LatBlock {
+    u64 count, calls, min_ticks, max_ticks, sum_ticks, max_iter, last_iters;   // mpx_lat's, accumulated
+    u64 raw_cap;            // iterations of a call whose end stamp is kept (host, at enable)
+    u64 raw_n;              // stamps of the last traced call in raw[]: 1 + min(iters, raw_cap)
+    unsigned hist[MPX_LAT_BUCKETS];
+    u64 raw[1];             // raw_cap + 1 stamps: t[0], then t[i+1] for i < raw_cap
+};
+inline size_t lat_block_bytes(int raw_cap) { return sizeof(LatBlock) + (size_t)raw_cap * sizeof(u64); }
+
 // Arguments of one transfer loop on one rank (kernel engine).
 struct XferArgs {
     const unsigned char* tx;     // local tx
@@ -192,6 +208,8 @@ struct XferArgs {
     u64 go_token;                // armed call: wait for Status.go == go_token first
                                  // (0: start at once)
     u64 go_timeout_ticks;        // armed call: how long the kernel waits for go
+    LatBlock* lat;               // the rank's latency recorder (mpx_lat_enable); null =
+                                 // tracing off, and then no _lat kernel is launched
 };
 
 // LL threshold of a link.  Within one GPU the bulk path's extra hop (payload

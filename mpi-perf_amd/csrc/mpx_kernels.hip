@@ -1202,17 +1202,105 @@ struct Loop {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Per-iteration latency recorder (mpx_lat_*, LatBlock): the blocking loops'
+// traced instantiations (k_xfer_lat, k_xfer_pull_lat).  Lane 0 of workgroup
+// 0 reads the clock once at the bottom of every iteration — where the
+// untraced loop stamps kTsFirst at i = 0, and for i = 0 that read IS the
+// kTsFirst stamp — and streams d = t[i+1] - t[i] into registers (min, max,
+// the iteration of the first maximum; the sum telescopes), one no-return
+// atomic add on its histogram bucket and, while i < raw_cap, one plain store
+// of the stamp: no load of the recorder stands in the loop.  Behind the
+// call's finish barrier it folds the registers into the rank's block (a plain
+// read-modify-write: a rank runs one call at a time, and the host touches
+// the block only between calls, on the rank's stream).
+// LatTrace<false> is empty: the untraced kernels read no clock for it.
+// ---------------------------------------------------------------------------
+// The clock read and its wait as ONE statement, fenced from the scheduler.
+__device__ __forceinline__ u64 lat_stamp() {
+    u64 t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+
+template <bool LAT>
+struct LatTrace {
+    __device__ bool on() const { return false; }
+    __device__ void begin(LatBlock*, u64, u64, int) {}
+    __device__ u64 tick(int) { return 0; }
+    __device__ void end() {}
+};
+template <>
+struct LatTrace<true> {
+    LatBlock* blk = nullptr;
+    u64 prev = 0, mn = ~0ull, mx = 0;   // (the sum telescopes: prev - t[0], taken at the end)
+    unsigned cap = 0, maxi = 0, n = 0;
+
+    __device__ bool on() const { return blockIdx.x == 0 && threadIdx.x == 0; }
+    // t[0]: the instant mpx_phases.first_iter_s counts from (complete_call's
+    // t_go): the peer's post on a side that pushes first, else the entry
+    __device__ __forceinline__ void begin(LatBlock* b, u64 t_entry, u64 t_posted, int iters) {
+        if (!on()) return;
+        blk = b;
+        prev = t_posted >= t_entry ? t_posted : t_entry;
+        // raw[] holds raw_cap + 1 stamps (lat_block_bytes): slot 0 here, slot
+        // i + 1 only while i < cap <= raw_cap (tick) — the one bound
+        const u64 rc = b->raw_cap;
+        cap = (u64)iters < rc ? (unsigned)iters : (unsigned)rc;
+        b->raw[0] = prev;
+    }
+    // the end of iteration i
+    __device__ __forceinline__ u64 tick(int i) {
+        const u64 t = lat_stamp();
+        const u64 d = t - prev;
+        prev = t;
+        if (d < mn) mn = d;
+        if (d > mx) {
+            mx = d;
+            maxi = (unsigned)i;
+        }
+        ++n;
+        __hip_atomic_fetch_add(&blk->hist[mpx_lat_bucket(d)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)i < cap) blk->raw[(unsigned)i + 1] = t;
+        return t;
+    }
+    __device__ __forceinline__ void end() {
+        if (!on()) return;
+        LatBlock& b = *blk;
+        const u64 c0 = b.count;
+        if (n) {
+            if (c0 == 0 || mn < b.min_ticks) b.min_ticks = mn;
+            if (c0 == 0 || mx > b.max_ticks) {
+                b.max_ticks = mx;
+                b.max_iter = maxi;
+            }
+            b.sum_ticks += prev - b.raw[0];
+            b.count = c0 + n;
+        }
+        b.calls += 1;
+        b.last_iters = n;
+        b.raw_n = 1 + (u64)(n < cap ? n : cap);
+    }
+};
+
 // One instantiation per (mode, side): each carries only its own loop, so
 // register pressure stays within 4 waves per SIMD (<= 128 VGPRs, no spills)
 // and four k_xfer workgroups fit on a CU — pairs that share one GPU
-// (loopback ranks, -g maps) keep every workgroup resident.
-template <int MODE, int GROUP>
-__global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
+// (loopback ranks, -g maps) keep every workgroup resident.  LAT: the traced
+// form (LatTrace); k_xfer is the LAT = false wrapper, k_xfer_lat the other.
+// The arguments come by value: the pull kernels then compile to the
+// instructions they had as kernels of their own, and the pushing sides load
+// their arguments once instead of at every use.
+template <int MODE, int GROUP, bool LAT>
+__device__ __forceinline__ void xfer_body(const XferArgs a) {
     __shared__ int s_abort;
     __shared__ u64 lds4[4];
     extern __shared__ v4u s_tx[];            // a.stage: dynamic LDS = one chunk
     if (threadIdx.x == 0) s_abort = 0;
     Loop<MODE> L{a, &s_abort, lds4, s_tx, {}};
+    LatTrace<LAT> T;
     if (!L.wait_go()) {
         if (L.last_to_finish()) L.finish_last();
         return;
@@ -1232,6 +1320,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
     // peer sent after it saw this side's post, so its peer has started too.
     constexpr bool push_first = MODE == MPX_MODE_NONBLOCKING || GROUP == 1;
     const bool go = !push_first || a.iters == 0 || L.wait_posted();
+    if constexpr (LAT) T.begin(a.lat, L.ts[kTsEntry], L.ts[kTsPosted], a.iters);
     // Group 1's last receive (ping-pong, unidir) without check mode: only
     // workgroup 0 waits for it (it counts receives and ends the call); the
     // others have nothing left to do once their last push is out, so they
@@ -1252,7 +1341,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
                 if (a.check) L.check(n, i);
                 L.send(n, ++txs, skip);                // Send(tx, B, tag 2)
             }
-            if (i == 0) L.stamp(kTsFirst);
+            if constexpr (LAT) {                       // one clock read: the iteration's end, and
+                if (T.on()) {                          // for i = 0 also the kTsFirst stamp
+                    const u64 t = T.tick(i);
+                    if (i == 0) L.ts[kTsFirst] = t;
+                }
+            } else if (i == 0) {
+                L.stamp(kTsFirst);
+            }
         } else if constexpr (MODE == MPX_MODE_UNIDIR) {  // mpi_perf.c:132-144
             if constexpr (GROUP == 1) {
                 L.send(n, ++txs, skip);                // Send(tx, B)
@@ -1266,7 +1362,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
                 if (a.check) { L.check(n, i); if (!L.grid_sync(i)) break; }
                 L.send(1, ++txs, skip);                // Send(tx, 1)
             }
-            if (i == 0) L.stamp(kTsFirst);
+            if constexpr (LAT) {                       // one clock read: the iteration's end, and
+                if (T.on()) {                          // for i = 0 also the kTsFirst stamp
+                    const u64 t = T.tick(i);
+                    if (i == 0) L.ts[kTsFirst] = t;
+                }
+            } else if (i == 0) {
+                L.stamp(kTsFirst);
+            }
         } else {                                       // mpi_perf.c:95-124
             // Isend + Irecv, slot `inflight`.  A receiver waits only at the
             // window flush (i = 255 mod 256) and at the end, so a push needs
@@ -1298,8 +1401,21 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
         if (L.last_to_finish()) L.finish_last();
     } else if (L.last_to_finish()) {
         L.account(done, (MODE == MPX_MODE_UNIDIR && GROUP == 1) ? 1 : n);
+        // (folded here, not right after the loop: there the traced ping-pong
+        // kernels came out with a 36-byte stack frame)
+        if constexpr (LAT) T.end();
         L.finish_last();
     }
+}
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
+    xfer_body<MODE, GROUP, false>(a);
+}
+// ping-pong and unidir only (launch_xfer): the non-blocking loop's iterations
+// have no blocking step to time
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_lat(XferArgs a) {
+    xfer_body<MODE, GROUP, true>(a);
 }
 
 // The non-blocking loop in check mode (mpi_perf.c:95-124 with every payload
@@ -1383,8 +1499,10 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_nbcheck(XferArgs a) {
 // unidir 1-byte ack (mpi_perf.c:137,142).  Grid: nwg for a side that
 // receives B-byte payloads, 1 for unidir group 1 (it only publishes and
 // takes acks).
-template <int MODE, int GROUP>
-__global__ __launch_bounds__(kBlock, 4) void k_xfer_pull(XferArgs a) {
+// LAT: the traced form (LatTrace), which also takes the kTsFirst and kTsLoop
+// stamps the untraced pull loop does not (mpx_phases.first_iter_s, tail_s).
+template <int MODE, int GROUP, bool LAT>
+__device__ __forceinline__ void xfer_pull_body(const XferArgs a) {
     __shared__ int s_abort;
     __shared__ u64 lds4[4];
     __shared__ u64 s_seen;
@@ -1393,6 +1511,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull(XferArgs a) {
         s_seen = 0;
     }
     Loop<MODE> L{a, &s_abort, lds4, nullptr, {}, &s_seen};
+    LatTrace<LAT> T;
     if (!L.wait_go()) {
         if (L.last_to_finish()) L.finish_last();
         return;
@@ -1406,6 +1525,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull(XferArgs a) {
     L.post_receives();
     bool ok = true;
     int inflight = 0;
+    if constexpr (LAT) T.begin(a.lat, L.ts[kTsEntry], L.ts[kTsPosted], a.iters);
     for (int i = 0; ok && i < a.iters; ++i) {
         if constexpr (MODE == MPX_MODE_PINGPONG) {    // mpi_perf.c:70-82
             if constexpr (GROUP == 1) {
@@ -1449,7 +1569,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull(XferArgs a) {
                 ++inflight;
             }
         }
+        if constexpr (LAT) {                           // the iteration's end on workgroup 0
+            if (ok && T.on()) {
+                const u64 t = T.tick(i);
+                if (i == 0) L.ts[kTsFirst] = t;
+            }
+        }
     }
+    if constexpr (LAT) L.stamp(kTsLoop);
     // every send of the call loaded by the peer before tx may change again
     const bool sent_bulk = MODE != MPX_MODE_UNIDIR || GROUP == 1;
     if (ok && sent_bulk && a.iters > 0 && !a.no_pull_wait) ok = L.wait_pulled(txs, a.iters - 1);
@@ -1476,8 +1603,17 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull(XferArgs a) {
         if (L.last_to_finish()) L.finish_last();
     } else if (L.last_to_finish()) {
         L.account(done, (MODE == MPX_MODE_UNIDIR && GROUP == 1) ? 1 : n);
+        if constexpr (LAT) T.end();
         L.finish_last();
     }
+}
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_pull(XferArgs a) {
+    xfer_pull_body<MODE, GROUP, false>(a);
+}
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_pull_lat(XferArgs a) {
+    xfer_pull_body<MODE, GROUP, true>(a);
 }
 
 // stream engines' receive accounting (launch_account)
@@ -1501,6 +1637,20 @@ __global__ __launch_bounds__(kBlock) void k_account(Status* st, const u64* csum,
 hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s) {
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
     void (*k)(XferArgs) = nullptr;
+    // tracing on (a.lat): the blocking loops' traced instantiations; the
+    // non-blocking loop has none and must not be handed a recorder
+    if (a.lat) {
+        if (a.mode != MPX_MODE_PINGPONG && a.mode != MPX_MODE_UNIDIR) return hipErrorInvalidValue;
+        const bool pp = a.mode == MPX_MODE_PINGPONG;
+        if (a.pull)
+            k = pp ? (a.group ? k_xfer_pull_lat<MPX_MODE_PINGPONG, 1> : k_xfer_pull_lat<MPX_MODE_PINGPONG, 0>)
+                   : (a.group ? k_xfer_pull_lat<MPX_MODE_UNIDIR, 1> : k_xfer_pull_lat<MPX_MODE_UNIDIR, 0>);
+        else
+            k = pp ? (a.group ? k_xfer_lat<MPX_MODE_PINGPONG, 1> : k_xfer_lat<MPX_MODE_PINGPONG, 0>)
+                   : (a.group ? k_xfer_lat<MPX_MODE_UNIDIR, 1> : k_xfer_lat<MPX_MODE_UNIDIR, 0>);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), a.pull ? 0u : (unsigned)a.stage, s, a);
+        return hipGetLastError();
+    }
     if (a.pull) {
         switch (a.mode) {
             case MPX_MODE_PINGPONG: k = a.group ? k_xfer_pull<MPX_MODE_PINGPONG, 1> : k_xfer_pull<MPX_MODE_PINGPONG, 0>; break;

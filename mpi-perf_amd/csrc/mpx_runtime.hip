@@ -234,7 +234,11 @@ struct Rank {
     size_t csum_cap = 0;
     unsigned char* ring = nullptr; // non-blocking check mode's receive slots 1..S-1
     uint64_t ring_bytes = 0;       //   (allocated on first use, or at export: ensure_ring)
-    std::vector<void*> retired;    // outgrown csum arrays (freed at finalize)
+    std::vector<void*> retired;    // outgrown csum arrays and recorder blocks (freed at finalize)
+    LatBlock* lat = nullptr;       // latency recorder (mpx_lat_enable), device memory
+    int lat_alloc = 0;             //   raw_cap the block was allocated for
+    int lat_cap = 0;               //   raw_cap in force
+    bool lat_on = false;           //   blocking calls of this rank are traced
     u64 tx_seq[MPX_MAX_RANKS] = {};
     u64 rx_seq[MPX_MAX_RANKS] = {};
     u64 calls[MPX_MAX_RANKS] = {};   // transfer calls on the link to that rank (Mailbox.posted)
@@ -887,6 +891,8 @@ int prepare_call(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank,
     a.ll_max = ll_max_bytes(same_device(me, peer));
     if (const char* v = getenv("MPX_LL_MAX")) a.ll_max = atoi(v) < kLLMaxBytes ? atoi(v) : kLLMaxBytes;
     a.cnt = me.cnt;
+    // the latency recorder traces the blocking loops only (launch_xfer)
+    a.lat = (me.lat_on && mode != MPX_MODE_NONBLOCKING) ? me.lat : nullptr;
     const TestKnobs knobs = test_knobs();
     a.skip_push = knobs.skip_push;
     a.no_pull_wait = knobs.no_pull_wait ? 1 : 0;
@@ -1645,6 +1651,7 @@ int mpx_finalize(mpx_ctx* ctx) {
         if (rk.ring) (void)hipFree(rk.ring);
         if (rk.scratch) (void)hipFree(rk.scratch);
         if (rk.csum) (void)hipFree(rk.csum);
+        if (rk.lat) (void)hipFree(rk.lat);
         for (void* q : rk.retired) (void)hipFree(q);
         if (rk.status) (void)hipHostFree(rk.status);
     }
@@ -1882,6 +1889,7 @@ void release_rank(Rank& rk) {
     if (rk.ring) (void)hipFree(rk.ring);
     if (rk.scratch) (void)hipFree(rk.scratch);
     if (rk.csum) (void)hipFree(rk.csum);
+    if (rk.lat) (void)hipFree(rk.lat);
     for (void* q : rk.retired) (void)hipFree(q);
     if (rk.status) (void)hipHostFree(rk.status);
     rk.ev0.reset();
@@ -2300,6 +2308,127 @@ int mpx_last_phases(mpx_ctx* ctx, int rank, mpx_phases* out) {
     if (!ctx || !out) return fail(MPX_ERR_INVALID, "NULL argument");
     if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) return fail(MPX_ERR_STATE, "rank %d is not a local rank", rank);
     *out = ctx->r[rank].phases;
+    return MPX_OK;
+}
+
+// ---- per-iteration latency recorder (include/mpx.h) -------------------------
+namespace {
+// The rank a recorder call names: local, and holding no armed call — an armed
+// kernel is already running on the rank's stream, which every recorder call
+// uses (and has read its recorder pointer).
+int lat_rank(mpx_ctx* ctx, int rank, Rank** out) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
+    if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) return fail(MPX_ERR_STATE, "rank %d is not a local rank", rank);
+    if (ctx->r[rank].armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", rank);
+    *out = &ctx->r[rank];
+    return MPX_OK;
+}
+// Statistics, histogram and raw count back to zero, raw_cap in force; on the
+// rank's stream, so the rank's next kernel starts behind it.
+int lat_clear(Rank& me) {
+    LatBlock h{};
+    h.raw_cap = (u64)me.lat_cap;
+    HIPCK(hipMemcpyAsync(me.lat, &h, offsetof(LatBlock, raw), hipMemcpyHostToDevice, me.stream));
+    HIPCK(hipStreamSynchronize(me.stream));
+    return MPX_OK;
+}
+int lat_header(Rank& me, LatBlock* h) {
+    // the rank's own stream: behind the rank's last kernel (an armed call's
+    // completion word comes before its kernel retires), and no wait for
+    // other ranks' kernels (finish_xfer)
+    HIPCK(hipMemcpyAsync(h, me.lat, offsetof(LatBlock, raw), hipMemcpyDeviceToHost, me.stream));
+    HIPCK(hipStreamSynchronize(me.stream));
+    return MPX_OK;
+}
+}  // namespace
+
+int mpx_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
+    if (ctx->engine != MPX_ENGINE_KERNEL)
+        return fail(MPX_ERR_UNSUPPORTED, "the latency recorder runs inside the kernel engine's loop: not this engine");
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    if (raw_cap < 0 || raw_cap > MPX_LAT_RAW_MAX) return fail(MPX_ERR_INVALID, "raw_cap %d not in [0,%d]", raw_cap, MPX_LAT_RAW_MAX);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    if (!me->lat || me->lat_alloc < raw_cap) {
+        // (no hipFree here: it waits for the whole device, ensure_csum)
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, lat_block_bytes(raw_cap));
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            return fail(MPX_ERR_NOMEM, "latency recorder of %zu B on device %d", lat_block_bytes(raw_cap), me->dev);
+        }
+        HIPCK(e);
+        if (me->lat) me->retired.push_back(me->lat);
+        me->lat = static_cast<LatBlock*>(p);
+        me->lat_alloc = raw_cap;
+    }
+    me->lat_cap = raw_cap;
+    me->lat_on = false;
+    TRY(lat_clear(*me));
+    me->lat_on = true;
+    return MPX_OK;
+}
+
+int mpx_lat_disable(mpx_ctx* ctx, int rank) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    me->lat_on = false;   // the block stays until finalize (no hipFree between calls)
+    return MPX_OK;
+}
+
+int mpx_lat_reset(mpx_ctx* ctx, int rank) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    if (!me->lat_on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    return lat_clear(*me);
+}
+
+int mpx_lat_get(mpx_ctx* ctx, int rank, mpx_lat* out) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
+    if (!me->lat_on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    LatBlock h{};
+    TRY(lat_header(*me, &h));
+    memset(out, 0, sizeof *out);
+    out->count = h.count;
+    out->calls = h.calls;
+    out->min_ticks = h.min_ticks;
+    out->max_ticks = h.max_ticks;
+    out->sum_ticks = h.sum_ticks;
+    out->max_iter = h.max_iter;
+    out->last_iters = h.last_iters;
+    out->tick_s = 1e-8;   // s_memrealtime: 100 MHz
+    static_assert(sizeof out->hist == sizeof h.hist, "mpx_lat and LatBlock histograms differ");
+    memcpy(out->hist, h.hist, sizeof h.hist);
+    return MPX_OK;
+}
+
+int mpx_lat_raw(mpx_ctx* ctx, int rank, uint64_t* stamps, int cap, int* n) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    if (!n || cap < 0 || (!stamps && cap > 0)) return fail(MPX_ERR_INVALID, "bad argument");
+    *n = 0;
+    if (!me->lat_on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    LatBlock h{};
+    TRY(lat_header(*me, &h));
+    // t[0] alone says nothing: with raw_cap = 0 no stamp is reported
+    u64 have = me->lat_cap > 0 ? h.raw_n : 0;
+    if (have > (u64)me->lat_cap + 1) have = (u64)me->lat_cap + 1;
+    if (have > (u64)cap) have = (u64)cap;
+    if (have) {
+        HIPCK(hipMemcpyAsync(stamps, me->lat->raw, (size_t)have * sizeof(u64), hipMemcpyDeviceToHost, me->stream));
+        HIPCK(hipStreamSynchronize(me->stream));
+    }
+    *n = (int)have;
     return MPX_OK;
 }
 

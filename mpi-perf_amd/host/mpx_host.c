@@ -29,6 +29,7 @@ void mpxh_defaults(mpxh_options *o)
     o->engine = 0;
     o->timeout_ms = 10000;
     o->arm = 1;
+    o->lat_cap = -1;
 }
 
 int mpxh_engine_from_name(const char *s)
@@ -66,7 +67,8 @@ void mpxh_print_usage(FILE *f)
 		    -c <checksum every payload 0|1|2 (2: seeded-pattern payloads)>\n\
 		    -S <min:max power-of-two message-size sweep>\n\
 		    -t <device wait timeout ms>\n\
-		    -A <launch each run's kernel before the barrier 0|1 (default 1)>\n");
+		    -A <launch each run's kernel before the barrier 0|1 (default 1)>\n\
+		    -L <raw-cap: record every iteration's latency, lat-*.csv (kernel engine, not -x 1)>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -75,7 +77,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -105,6 +107,13 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
         case 't': o->timeout_ms = atoi(optarg); break;
         case 'g': strncpy(o->gpus, optarg, sizeof o->gpus - 1); break;
         case 'A': o->arm = atoi(optarg); break;
+        case 'L': {
+            char *end = NULL;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > (1 << 22)) return MPXH_PARSE_BAD_VALUE; /* MPX_LAT_RAW_MAX */
+            o->lat_cap = (int)v;
+            break;
+        }
         default: return MPXH_PARSE_USAGE; /* includes -h and a missing value */
         }
     }
@@ -112,9 +121,16 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     return MPXH_PARSE_OK;
 }
 
-/* mpi_perf.c:399-403 */
+/* mpi_perf.c:399-403; first the one rule of the new flags that needs two of
+   them: -L traces the kernel engine's blocking loops only */
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
+    if (o->lat_cap >= 0 && (o->nonblocking || o->engine != 0)) {
+        fprintf(err, "invalid -L %d with %s: per-iteration latencies are recorded by the kernel engine's "
+                     "ping-pong and unidir loops only\n",
+                o->lat_cap, o->engine != 0 ? "-e sdma|rccl" : "-x 1");
+        return 1;
+    }
     if (o->group_size <= 0) goto invalid;
     if (!o->uni_dir) {
         if (o->ppn == 0) return 2; /* world_size / (2 * ppn): integer division by zero */
@@ -259,6 +275,16 @@ int mpxh_format_record(char *out, size_t cap, const char *timestamp, const char 
 {
     return snprintf(out, cap, "%s,%s,%d,%d,%s,%s,%d,%d,%d,%.2lf,%lld\n", timestamp, uuid, world_rank,
                     world_size / ppn, local_ip, remote_ip, ppn, buff_len, iters, my_time_s * 1000.0, run_idx);
+}
+
+/* one line of lat-*.csv; us[] = min, p50, p90, p99, p99.9, max, mean */
+int mpxh_format_lat(char *out, size_t cap, const char *timestamp, const char *uuid, int rank, int peer, int mode,
+                    int buff_len, int iters, long long run_idx, unsigned long long count, const double us[7],
+                    unsigned long long max_iter)
+{
+    return snprintf(out, cap, "%s,%s,%d,%d,%d,%d,%d,%lld,%llu,%.2f,%.2f,%.2f,%.2f,%.2f,%.2f,%.3f,%llu\n", timestamp,
+                    uuid, rank, peer, mode, buff_len, iters, run_idx, count, us[0], us[1], us[2], us[3], us[4], us[5],
+                    us[6], max_iter);
 }
 
 /* mpi_perf.c:494 */

@@ -43,6 +43,9 @@ typedef struct mpxh_options {
     char gpus[256];                 /* -g  rank->GPU list "0,1,..."          */
     int arm;                        /* -A  1 (default) = arm each run's kernel
                                            before the barrier (mpx_xfer_arm) */
+    int lat_cap;                    /* -L  raw_cap: record every iteration's
+                                           latency (mpx_lat_*), lat-*.csv;
+                                           -1 (default) = off                */
 } mpxh_options;
 
 /* parse status */
@@ -57,7 +60,7 @@ enum {
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -65,7 +68,8 @@ void mpxh_print_usage(FILE *f);
 int mpxh_engine_from_name(const char *s);
 const char *mpxh_engine_name(int e);
 
-/* validate group_size, mpi_perf.c:399-403.  Returns:
+/* validate group_size, mpi_perf.c:399-403, then -L against -x / -e (the
+   recorder traces the kernel engine's blocking loops only).  Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides
    by zero here (ppn == 0 in bidirectional mode): the caller raises SIGFPE. */
 int mpxh_validate(const mpxh_options *o, int world, FILE *err);
@@ -96,6 +100,13 @@ int mpxh_parse_gpu_list(const char *s, int *devs, int n);
 
 /* time strings, getformatted_time mpi_perf.c:341-353 */
 void mpxh_format_time(char *buf, size_t cap, int for_kusto);
+/* lat-*.csv (-L): header, and one line per recorded run; times in us */
+#define MPXH_LAT_HEADER                                                                                   \
+    "Timestamp,JobId,Rank,PeerRank,Mode,BufferSize,NumOfBuffers,RunId,Count,MinUs,P50Us,P90Us,P99Us,P999Us," \
+    "MaxUs,MeanUs,MaxIter\n"
+int mpxh_format_lat(char *out, size_t cap, const char *timestamp, const char *uuid, int rank, int peer, int mode,
+                    int buff_len, int iters, long long run_idx, unsigned long long count, const double us[7],
+                    unsigned long long max_iter);
 /* record line, mpi_perf.c:550-554 */
 int mpxh_format_record(char *out, size_t cap, const char *timestamp, const char *uuid, int world_rank,
                        int world_size, int ppn, const char *local_ip, const char *remote_ip, int buff_len,

@@ -215,6 +215,7 @@ static void ingest_hook(int rank)
 typedef struct {
     FILE *log_fp, *gpu_fp;
     double t_last_logtime;
+    FILE *lat_fp; /* -L: the per-iteration latency side file */
 } rank_files;
 
 static void open_logs(int rank, rank_files *f)
@@ -224,6 +225,7 @@ static void open_logs(int rank, rank_files *f)
         fclose(f->log_fp);
     }
     if (f->gpu_fp) fclose(f->gpu_fp);
+    if (f->lat_fp) fclose(f->lat_fp);
     ingest_hook(rank);
     char ft[26] = {0};
     char name[2 * MPXH_MAX_HOST + 64];
@@ -238,6 +240,14 @@ static void open_logs(int rank, rank_files *f)
         fprintf(f->gpu_fp, "Timestamp,JobId,Rank,Engine,Mode,Device,PeerRank,PeerDevice,BufferSize,NumOfBuffers,"
                            "WallTimems,DeviceTimems,GBps,Protocol,Workgroups,CheckedPayloads,CheckFailures,RunId,RecvDone,"
                            "RecvDigest,Launch,Rccl\n");
+    /* -L: the latency side file, opened and rotated with the GPU side file
+       (a name of its own: neither "tcp*" nor "gpu-*.csv" matches it) */
+    f->lat_fp = NULL;
+    if (opt.lat_cap >= 0) {
+        snprintf(name, sizeof name, "%s/lat-%s-%d-%s.csv", opt.logfolder, opt.uuid, rank, ft);
+        f->lat_fp = fopen(name, "w");
+        if (f->lat_fp) fputs(MPXH_LAT_HEADER, f->lat_fp);
+    }
     f->t_last_logtime = wtime();
 }
 
@@ -265,8 +275,10 @@ static int xfer_mode(void)
 static void *rank_main(void *arg)
 {
     const int r = (int)(intptr_t)arg;
-    rank_files files = {NULL, NULL, wtime()};
+    rank_files files = {NULL, NULL, wtime(), NULL};
     int prev_group = -1;
+    const int lat = opt.lat_cap >= 0 && !opt.use_dotnet;
+    if (lat) MPX_CHECK(mpx_lat_enable(ctx, r, opt.lat_cap));
     for (int si = 0; si < nsizes; ++si) {
         const int B = sizes[si];
         for (long long run_idx = 0; opt.num_runs == -1 || run_idx < opt.num_runs; run_idx++) {
@@ -308,6 +320,9 @@ static void *rank_main(void *arg)
                inside the timed call (the reference's timer brackets only the
                loop, mpi_perf.c:501-533) */
             if (!opt.use_dotnet) MPX_CHECK(mpx_xfer_prepare(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo));
+            /* -L: every run's distribution is its own (before the arm: an
+               armed rank's recorder cannot be touched) */
+            if (lat) MPX_CHECK(mpx_lat_reset(ctx, r));
             /* -A 1: the run's kernel is launched now and started by the
                mpx_xfer_ex after the barrier (MPI_Start of a persistent
                request), so the launch is not inside the timed loop */
@@ -350,6 +365,21 @@ static void *rank_main(void *arg)
                             (unsigned long long)tm.recv_done, (unsigned long long)tm.recv_digest,
                             (opt.arm && opt.engine == MPX_ENGINE_KERNEL) ? "armed" : "inline", rccl_build);
                 }
+                if (lat && files.lat_fp) {
+                    mpx_lat l;
+                    MPX_CHECK(mpx_lat_get(ctx, r, &l));
+                    const double us_tick = l.tick_s * 1e6;
+                    const double us[7] = {(double)l.min_ticks * us_tick,
+                                          (double)mpx_lat_quantile(&l, 0.5) * us_tick,
+                                          (double)mpx_lat_quantile(&l, 0.9) * us_tick,
+                                          (double)mpx_lat_quantile(&l, 0.99) * us_tick,
+                                          (double)mpx_lat_quantile(&l, 0.999) * us_tick,
+                                          (double)l.max_ticks * us_tick,
+                                          l.count ? (double)l.sum_ticks * us_tick / (double)l.count : 0.0};
+                    mpxh_format_lat(line, sizeof line, ts, opt.uuid, r, peer, xfer_mode(), B, opt.iters, run_idx,
+                                    (unsigned long long)l.count, us, (unsigned long long)l.max_iter);
+                    fputs(line, files.lat_fp);
+                }
             }
 
             time_of[r] = my_time;
@@ -378,6 +408,7 @@ static void *rank_main(void *arg)
     }
     if (files.log_fp) fclose(files.log_fp);
     if (files.gpu_fp) fclose(files.gpu_fp);
+    if (files.lat_fp) fclose(files.lat_fp);
     return NULL;
 }
 
@@ -520,7 +551,7 @@ int main(int argc, char **argv)
     }
     if (pst == MPXH_PARSE_BAD_VALUE) {
         if (is_root()) {
-            fprintf(stderr, "bad value for -e / -S\n");
+            fprintf(stderr, "bad value for -e / -S / -L\n");
             mpxh_print_usage(stderr);
         }
         mpx_abort();

@@ -79,6 +79,58 @@ class Phases(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+LAT_BUCKETS = 464
+LAT_RAW_MAX = 1 << 22
+
+
+class Lat(C.Structure):
+    """mpx_lat: a rank's per-iteration latency distribution (ticks of 10 ns)"""
+    _fields_ = ([(k, C.c_uint64) for k in ("count", "calls", "min_ticks", "max_ticks", "sum_ticks", "max_iter",
+                                            "last_iters")]
+                + [("tick_s", C.c_double), ("hist", C.c_uint32 * LAT_BUCKETS)])
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["hist"] = list(self.hist)
+        return d
+
+
+def lat_bucket(v: int) -> int:
+    """mpx_lat_bucket (include/mpx.h): the histogram bucket of v ticks"""
+    if v < 32:
+        return v
+    if v >> 32:
+        return LAT_BUCKETS - 1
+    e = v.bit_length() - 1
+    return 32 + (e - 5) * 16 + ((v >> (e - 4)) & 15)
+
+
+def lat_bucket_floor(b: int) -> int:
+    """mpx_lat_bucket_floor: the smallest value of bucket b"""
+    if b < 32:
+        return max(b, 0)
+    return (16 + (b - 32) % 16) << ((b - 32) // 16 + 1)
+
+
+def lat_quantile(lat: dict, q: float) -> int:
+    """mpx_lat_quantile over a lat_get() dict: ticks"""
+    count = lat["count"]
+    if count == 0:
+        return 0
+    x = min(max(q, 0.0), 1.0) * float(count)
+    want = int(x)
+    if float(want) < x:
+        want += 1
+    cum, b = 0, 0
+    for b in range(LAT_BUCKETS - 1):
+        cum += lat["hist"][b]
+        if cum >= want:
+            break
+    else:
+        b = LAT_BUCKETS - 1
+    return min(max(lat_bucket_floor(b), lat["min_ticks"]), lat["max_ticks"])
+
+
 def pattern_key(seed: int, src: int, dst: int, it: int) -> int:
     """mpx_pattern_key (include/mpx.h)."""
     return (seed ^ (src << 56) ^ (dst << 48) ^ (it << 24)) & 0xFFFFFFFFFFFFFFFF
@@ -115,6 +167,11 @@ _SIGS = {
                                C.c_int, C.POINTER(XferOpts)]),
     "mpx_xfer_disarm": (C.c_int, [C.c_void_p, C.c_int]),
     "mpx_barrier": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_lat_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mpx_lat_disable": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_lat_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_lat_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Lat)]),
+    "mpx_lat_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mpx_rccl_get_unique_id": (C.c_int, [C.c_void_p]),
     "mpx_rccl_init_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -207,6 +264,7 @@ class Context:
         check(self.L.mpx_init(nranks, engine, C.byref(self.h)), "mpx_init")
         self.nranks = nranks
         self.engine = engine
+        self._lat_cap = {}   # rank -> raw_cap of its latency recorder (lat_enable)
 
     def close(self) -> None:
         if self.h:
@@ -307,6 +365,35 @@ class Context:
         p = Phases()
         check(self.L.mpx_last_phases(self.h, rank, C.byref(p)), "mpx_last_phases")
         return p.as_dict()
+
+    # per-iteration latency recorder (kernel engine)
+    def lat_enable(self, rank: int, raw_cap: int = 0) -> None:
+        """mpx_lat_enable: trace rank's ping-pong / unidir calls from now on,
+        keeping the first raw_cap iterations' stamps of each call; resets"""
+        check(self.L.mpx_lat_enable(self.h, rank, raw_cap), "mpx_lat_enable")
+        self._lat_cap[rank] = raw_cap
+
+    def lat_disable(self, rank: int) -> None:
+        check(self.L.mpx_lat_disable(self.h, rank), "mpx_lat_disable")
+
+    def lat_reset(self, rank: int) -> None:
+        check(self.L.mpx_lat_reset(self.h, rank), "mpx_lat_reset")
+
+    def lat_get(self, rank: int) -> dict:
+        """mpx_lat_get: the distribution accumulated since enable / reset"""
+        l = Lat()
+        check(self.L.mpx_lat_get(self.h, rank, C.byref(l)), "mpx_lat_get")
+        return l.as_dict()
+
+    def lat_raw(self, rank: int, cap: int | None = None) -> list[int]:
+        """mpx_lat_raw: the last traced call's stamps t[0 .. min(iters, raw_cap)]
+        (cap: at most that many; default all of them)"""
+        if cap is None:
+            cap = self._lat_cap.get(rank, 0) + 1
+        n = C.c_int(0)
+        buf = (C.c_uint64 * max(cap, 1))()
+        check(self.L.mpx_lat_raw(self.h, rank, buf, cap, C.byref(n)), "mpx_lat_raw")
+        return list(buf[:n.value])
 
     def rccl_init_all(self) -> None:
         check(self.L.mpx_rccl_init_all(self.h), "mpx_rccl_init_all")
