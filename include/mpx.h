@@ -209,10 +209,12 @@ int mpx_live_events(int *count);
 int mpx_alloc(mpx_ctx *ctx, int dev, size_t bytes, void **ptr);
 /* free() analogue (mpi_perf.c:576-577) */
 int mpx_free(mpx_ctx *ctx, void *ptr);
-/* memset analogue (mpi_perf.c:246,250); see enum mpx_fill */
+/* memset analogue (mpi_perf.c:246,250); see enum mpx_fill.  `ptr` must be
+   8-byte aligned (n > 0): MPX_ERR_INVALID otherwise, before any launch. */
 int mpx_fill(mpx_ctx *ctx, int dev, void *ptr, size_t n, int pattern, uint64_t arg);
 /* order-independent 64-bit checksum of n bytes (definition in DESIGN.md and
-   oracle/mpx_oracle.c: oracle_checksum) */
+   oracle/mpx_oracle.c: oracle_checksum).  `ptr` must be 16-byte aligned
+   (n > 0): MPX_ERR_INVALID otherwise, before any launch. */
 int mpx_checksum(mpx_ctx *ctx, int dev, const void *ptr, size_t n, uint64_t *out);
 /* device -> host copy, for tests */
 int mpx_read(mpx_ctx *ctx, int dev, void *host_dst, const void *dev_src, size_t n);

@@ -1747,6 +1747,7 @@ int mpx_free(mpx_ctx* ctx, void* ptr) {
 int mpx_fill(mpx_ctx* ctx, int dev, void* ptr, size_t n, int pattern, uint64_t arg) {
     if (!ctx || (!ptr && n)) return fail(MPX_ERR_INVALID, "NULL argument");
     if (pattern != MPX_FILL_BYTE && pattern != MPX_FILL_SPLITMIX) return fail(MPX_ERR_INVALID, "pattern %d", pattern);
+    if (n && (reinterpret_cast<uintptr_t>(ptr) & 7)) return fail(MPX_ERR_INVALID, "fill buffer must be 8-byte aligned");
     TRY(check_dev(dev));
     if (!n) return MPX_OK;
     hipStream_t s;
@@ -1760,6 +1761,8 @@ int mpx_fill(mpx_ctx* ctx, int dev, void* ptr, size_t n, int pattern, uint64_t a
 
 int mpx_checksum(mpx_ctx* ctx, int dev, const void* ptr, size_t n, uint64_t* out) {
     if (!ctx || !out || (!ptr && n)) return fail(MPX_ERR_INVALID, "NULL argument");
+    if (n && (reinterpret_cast<uintptr_t>(ptr) & 15))
+        return fail(MPX_ERR_INVALID, "checksum buffer must be 16-byte aligned");
     TRY(check_dev(dev));
     hipStream_t s;
     TRY(util_stream(ctx, dev, &s));

@@ -239,7 +239,8 @@ def test_loopback_pair_every_payload(engine, mode):
 # <= 60 KiB are pushed from LDS (stage_tx), larger ones straight from HBM; a
 # width wider than B / 1 KiB is narrowed to that (run_kernel, kMinPushChunk)
 PUSH_CASES = [(1, 40000), (1, 70001), (7, 456131), (8, 456131), (33, (1 << 20) + 17), (128, (4 << 20) + 3),
-              (256, (20 << 20) + 5), (64, 20000), (256, 3000)]
+              (256, (20 << 20) + 5), (64, 20000), (256, 3000),
+              (256, 456131), (70, 71681)]   # the last workgroup's chunk is empty (tests/payload.py)
 
 
 @pytest.mark.parametrize("stream", [False, True])

@@ -67,7 +67,8 @@ def test_pull_pair_every_payload(mode, engine):
 # (workgroups, B): chunk = ceil(B / nwg) rounded up to 16 B, pulled 8 units
 # per lane at a time; ragged tails; a width wider than B / 1 KiB is narrowed
 PULL_CASES = [(1, 40000), (1, 70001), (7, 456131), (8, 456131), (33, (1 << 20) + 17), (128, (4 << 20) + 3),
-              (256, (20 << 20) + 5), (64, 20000), (256, 3000)]
+              (256, (20 << 20) + 5), (64, 20000), (256, 3000),
+              (256, 456131), (70, 71681)]   # the last workgroup's chunk is empty (tests/payload.py)
 
 
 @pytest.mark.parametrize("mode", MODES)
