@@ -200,6 +200,33 @@ int mpx_shutdown(void);
    (each is owned by an RAII holder and destroyed on every return path:
    the tests' leak check around a failing mpx_copy, MPX_TEST=fail_copy). */
 int mpx_live_events(int *count);
+/* Diagnostic, read-only, always available: the counters of the link between
+   local rank `my_rank` and `peer_rank`, as the next call will find them:
+     out[0]  pushes my_rank has made on the link (its last push's number)
+     out[1]  pushes it has received on the link
+     out[2]  transfer calls made on the link (the receive-posted number)
+     out[3]  kernel-engine calls my_rank has made on any link (its token)
+   Each grows by the iterations of a completed call (out[0], out[1]), by one
+   per call with iters > 0 (out[2]) or by one per kernel-engine call (out[3]);
+   a call that failed before its launch leaves all four as they were.
+   MPX_ERR_INVALID: my_rank is not a local rank of this context (an imported
+   rank's counters live in its own process), or peer_rank is out of range.
+   Call it between calls of my_rank, not while one runs. */
+int mpx_link_counters(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t out[4]);
+/* TEST ONLY: adds seq_by to out[0] and out[1] above, calls_by to out[2] and
+   token_by to out[3] — the state a link reaches after that many pushes and
+   calls, without running them.  It only adds: no counter is set or goes back
+   (MPX_ERR_INVALID if one would pass 2^64).  BOTH ranks of a link must be
+   advanced alike before their next call (each process its own side), or
+   that call waits out its deadline.  Not to be used so that an LL message
+   follows a larger one by an exact multiple of 2^31 pushes.
+   MPX_ERR_UNSUPPORTED unless the process started with MPX_TEST in its
+   environment (the once-per-process gate of the fault-injection knobs:
+   mpx_perf and bench.py can never reach it); MPX_ERR_INVALID for a rank that
+   is not local; MPX_ERR_STATE for a rank that holds an armed call or whose
+   transfer timed out. */
+int mpx_test_advance_link(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t seq_by, uint64_t calls_by,
+                          uint64_t token_by);
 
 /* ---- buffers (allocate_tx_rx_buffers, mpi_perf.c:240-252) ---------------- */
 /* posix_memalign(4096) analogue: device memory on `dev`, 4 KiB aligned.  The

@@ -473,7 +473,8 @@ u64 nb_waited(int iters) {
 // Whether the variable exists is read ONCE per process: a process that
 // starts without it (bench.py, mpx_perf) never looks again, and none of the
 // knobs can reach it.  The tests set it (empty) before their first call
-// (tests/conftest.py) and change its value between calls.
+// (tests/conftest.py) and change its value between calls.  The same gate
+// (test_gate) guards mpx_test_advance_link.
 struct TestKnobs {
     int skip_push = 0;
     int lag_rank = -1, lag_wg = 0;
@@ -482,10 +483,13 @@ struct TestKnobs {
     int fail_launch = -1;
     bool fail_copy = false;
 };
-TestKnobs test_knobs() {
+bool test_gate() {
     static const bool gate = getenv("MPX_TEST") != nullptr;
+    return gate;
+}
+TestKnobs test_knobs() {
     TestKnobs k;
-    if (!gate) return k;
+    if (!test_gate()) return k;
     const char* v = getenv("MPX_TEST");
     if (!v) return k;
     std::string all(v);
@@ -2304,6 +2308,46 @@ int mpx_shutdown(void) {
 int mpx_live_events(int* count) {
     if (!count) return fail(MPX_ERR_INVALID, "NULL argument");
     *count = live_events().load();
+    return MPX_OK;
+}
+
+int mpx_link_counters(mpx_ctx* ctx, int my_rank, int peer_rank, uint64_t out[4]) {
+    if (!ctx || !out) return fail(MPX_ERR_INVALID, "NULL argument");
+    if (my_rank < 0 || my_rank >= ctx->nranks || !ctx->r[my_rank].local)
+        return fail(MPX_ERR_INVALID, "rank %d is not a local rank", my_rank);
+    if (peer_rank < 0 || peer_rank >= ctx->nranks) return fail(MPX_ERR_INVALID, "peer rank %d", peer_rank);
+    const Rank& me = ctx->r[my_rank];
+    out[0] = me.tx_seq[peer_rank];
+    out[1] = me.rx_seq[peer_rank];
+    out[2] = me.calls[peer_rank];
+    out[3] = me.token;
+    return MPX_OK;
+}
+
+// Test-only (the MPX_TEST gate of test_knobs): the link's counters jump
+// forward, as a long run would have left them.  Every mailbox compare is
+// "word >= a value derived from these counters" and the mailbox holds only
+// values of the link's past, so a forward jump made alike on both ranks of the
+// link is a state the link can reach (the one exception: the LL
+// zone's 2^31 alias).
+int mpx_test_advance_link(mpx_ctx* ctx, int my_rank, int peer_rank, uint64_t seq_by, uint64_t calls_by,
+                          uint64_t token_by) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "NULL argument");
+    if (!test_gate()) return fail(MPX_ERR_UNSUPPORTED, "mpx_test_advance_link: the process started without MPX_TEST");
+    if (my_rank < 0 || my_rank >= ctx->nranks || !ctx->r[my_rank].local)
+        return fail(MPX_ERR_INVALID, "rank %d is not a local rank", my_rank);
+    if (peer_rank < 0 || peer_rank >= ctx->nranks) return fail(MPX_ERR_INVALID, "peer rank %d", peer_rank);
+    Rank& me = ctx->r[my_rank];
+    if (me.armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", my_rank);
+    if (me.broken) return fail(MPX_ERR_STATE, "rank %d: a previous transfer timed out", my_rank);
+    const u64 top = ~0ull;
+    if (seq_by > top - me.tx_seq[peer_rank] || seq_by > top - me.rx_seq[peer_rank] ||
+        calls_by > top - me.calls[peer_rank] || token_by > top - me.token)
+        return fail(MPX_ERR_INVALID, "rank %d: a counter would pass 2^64", my_rank);
+    me.tx_seq[peer_rank] += seq_by;
+    me.rx_seq[peer_rank] += seq_by;
+    me.calls[peer_rank] += calls_by;
+    me.token += token_by;
     return MPX_OK;
 }
 

@@ -148,6 +148,8 @@ _SIGS = {
     "mpx_finalize": (C.c_int, [C.c_void_p]),
     "mpx_shutdown": (C.c_int, []),
     "mpx_live_events": (C.c_int, [C.POINTER(C.c_int)]),
+    "mpx_link_counters": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "mpx_test_advance_link": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64]),
     "mpx_alloc": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     "mpx_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mpx_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64]),
@@ -365,6 +367,20 @@ class Context:
         p = Phases()
         check(self.L.mpx_last_phases(self.h, rank, C.byref(p)), "mpx_last_phases")
         return p.as_dict()
+
+    def link_counters(self, my_rank: int, peer_rank: int) -> dict:
+        """mpx_link_counters: the link's push and call counters and my_rank's
+        token, as whole 64-bit numbers"""
+        out = (C.c_uint64 * 4)()
+        check(self.L.mpx_link_counters(self.h, my_rank, peer_rank, out), "mpx_link_counters")
+        return dict(tx_seq=int(out[0]), rx_seq=int(out[1]), calls=int(out[2]), token=int(out[3]))
+
+    def test_advance_link(self, my_rank: int, peer_rank: int, seq_by: int = 0, calls_by: int = 0,
+                          token_by: int = 0) -> None:
+        """mpx_test_advance_link (test only, MPX_TEST gate): the counters jump
+        forward; both ranks of a link alike"""
+        check(self.L.mpx_test_advance_link(self.h, my_rank, peer_rank, seq_by, calls_by, token_by),
+              "mpx_test_advance_link")
 
     # per-iteration latency recorder (kernel engine)
     def lat_enable(self, rank: int, raw_cap: int = 0) -> None:

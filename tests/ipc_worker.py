@@ -3,6 +3,11 @@
 Each process owns one mpx context with one local rank on GPU 0, exports its
 descriptor to a file, imports the other rank's, then runs every loop mode
 with every payload checksummed.  Results go to <dir>/result_<rank>.json.
+
+Two further arguments, <seq_by> <bytes> (tests/test_gpu_wrap.py): right after
+attach and import each process advances its own side of the link by seq_by
+pushes (mpx_test_advance_link), then runs one ping-pong and one unidir call
+of 9 iterations of that size, and records the link's counters around each.
 """
 import json
 import os
@@ -16,6 +21,31 @@ import mpx  # noqa: E402
 
 # 8191 / 8192 / 8193: both sides of the cross-GPU LL threshold (ll_max_bytes)
 SIZES = (1, 8, 4097, 8191, 8192, 8193, 65541, 1 << 20)
+
+
+def advanced(c, d, rank, peer, group, tx, rx, peer_sums, seq_by, n):
+    c.test_advance_link(rank, peer, seq_by, 0, 0)
+    try:
+        c.link_counters(peer, rank)
+        imported = mpx.OK
+    except mpx.MpxError as e:
+        imported = e.status
+    # the peer's tx, from the host's restatement of its fill
+    import oracle_py as O
+    theirs = O.fill(n, mpx.FILL_SPLITMIX, mpx.pattern_key(mpx.PATTERN_SEED, peer, rank, 0))
+    assert O.checksum(theirs[:1]) == peer_sums["1"]
+    results = []
+    for mode in (mpx.MODE_PINGPONG, mpx.MODE_UNIDIR):
+        before = c.link_counters(rank, peer)
+        t = c.xfer(mode, group, rank, peer, 9, tx, rx, n, check_payload=True, expect=O.checksum(theirs),
+                   expect_ack=O.checksum(theirs[:1]), timeout_ms=5000)
+        m = 1 if (mode == mpx.MODE_UNIDIR and group == 1) else n
+        results.append(dict(mode=mode, n=n, iters=9, check_iters=t.check_iters, check_failures=t.check_failures,
+                            recv_done=t.recv_done, final_rx_ok=c.read(rx, m) == theirs[:m],
+                            protocol=t.protocol, before=before, after=c.link_counters(rank, peer),
+                            imported_rank_status=imported))
+    with open(os.path.join(d, f"result_{rank}.json"), "w") as f:
+        json.dump(results, f)
 
 
 def main():
@@ -47,6 +77,10 @@ def main():
         time.sleep(0.01)
     c.import_rank(peer, open(os.path.join(d, f"desc_{peer}.bin"), "rb").read())
     peer_sums = json.load(open(os.path.join(d, f"sums_{peer}.json")))
+    if len(sys.argv) > 6:
+        advanced(c, d, rank, peer, group, tx, rx, peer_sums, int(sys.argv[5]), int(sys.argv[6]))
+        c.close()
+        return
     results = []
     for mode in (mpx.MODE_PINGPONG, mpx.MODE_UNIDIR, mpx.MODE_NONBLOCKING):
         for n in SIZES:

@@ -47,6 +47,24 @@ EDGE_CASES = {
     (256, (1 << 20) + 1): (256, 4112, 0, 255, 17),  # one unit + 1
 }
 
+NB_WINDOW = 256           # kNbWindow (mpx_internal.h)
+
+
+def ring_bytes_for(length: int, cap: int = 64 << 20) -> int:
+    """bytes of the check-mode receive ring of a rank attached with `length`
+    bytes (ring_bytes_for, mpx_runtime.hip): whole slots of the attached
+    length, at most 255, within `cap` = MPX_CHECK_RING_BYTES"""
+    if length == 0:
+        return 0
+    return min((NB_WINDOW - 1) * length, cap) // length * length
+
+
+def ring_slots(ring_bytes: int, n: int) -> int:
+    """receive slots of a link for messages of n bytes (ring_slots,
+    mpx_internal.h): rx itself and every whole message the ring holds"""
+    return NB_WINDOW if n <= 0 else min(NB_WINDOW, 1 + ring_bytes // n)
+
+
 _hip = None
 
 

@@ -35,6 +35,29 @@ def test_every_header_symbol_is_exported():
         assert f" T {s}\n" in dyn or f" T {s}" in dyn, s
 
 
+def test_link_counter_symbols_declared_exported_and_bound():
+    """mpx_link_counters (diagnostic) and mpx_test_advance_link (test only):
+    in the header, exported, in the binding's table with 64-bit counters; no
+    ABI bump — callers detect them by symbol, as for mpx_lat_*"""
+    names = ["mpx_link_counters", "mpx_test_advance_link"]
+    assert [s for s in mpx.header_symbols() if s in names] == names
+    dyn = subprocess.run(["nm", "-D", "--defined-only", mpx.LIB_PATH], capture_output=True, text=True).stdout
+    for s in names:
+        assert f" T {s}\n" in dyn, s
+    assert mpx.lib().mpx_version() == 7
+    assert mpx._SIGS["mpx_link_counters"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)])
+    assert mpx._SIGS["mpx_test_advance_link"] == (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_uint64] * 3)
+    txt = open(mpx.HEADER_PATH).read()
+    assert "int mpx_link_counters(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t out[4]);" in txt
+    assert ("int mpx_test_advance_link(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t seq_by, uint64_t calls_by,\n"
+            "                          uint64_t token_by);") in txt
+    # argument checks that return before any GPU call
+    L = mpx.lib()
+    out = (C.c_uint64 * 4)()
+    assert L.mpx_link_counters(None, 0, 1, out) == mpx.ERR_INVALID
+    assert L.mpx_test_advance_link(None, 0, 1, 1, 1, 1) == mpx.ERR_INVALID
+
+
 def test_counter_library_exports_its_header():
     """libmpxprof.so (bench.py's in-process counters) exports every function
     include/mpxprof.h declares; loading it starts nothing (no HIP here)."""

@@ -22,63 +22,14 @@ import pytest
 import mpx
 import oracle_py as O
 import payload
-from pairs import Pairs
+from hostpairs import HostPairs, run_checked
 from payload import assert_region, chunk_shape, sub
 
 pytestmark = pytest.mark.gpu
 
-M64 = 0xFFFFFFFFFFFFFFFF
 PINGPONG, NONBLOCKING, UNIDIR = mpx.MODE_PINGPONG, mpx.MODE_NONBLOCKING, mpx.MODE_UNIDIR
 PROTO_LL, PROTO_BULK, PROTO_PULL = 0, 1, 7
 GUARD = payload.GUARD
-
-
-class HostPairs(Pairs):
-    """one loopback pair of the kernel engine with seeded tx, whose expected
-    bytes and checksums all come from the host: host[r] = what rank r's tx
-    holds"""
-
-    def __init__(self, cap):
-        super().__init__("kernel", 1, cap, fill="seeded")
-        self.host = [O.fill(cap, mpx.FILL_SPLITMIX, mpx.pattern_key(mpx.PATTERN_SEED, r, 0, 0)) for r in (0, 1)]
-
-    def set_tx(self, data: bytes):
-        """both ranks' tx[0 : len(data)) = data (between calls)"""
-        for r in (0, 1):
-            payload.write(self.c, self.bufs[r][0], data)
-            self.host[r] = data + self.host[r][len(data):]
-
-    def expect(self, r, n):
-        """what check mode is told to expect: host checksums of the peer's tx"""
-        h = self.host[self.peer(r)]
-        return O.checksum(h[:n]), O.checksum(h[:1])
-
-
-def received(mode, r, n):
-    """bytes rank r receives per message: B, or unidir's 1-byte ack (rank 0 =
-    group 1, mpi_perf.c:137,142)"""
-    return 1 if (mode == UNIDIR and r == 0) else n
-
-
-def run_checked(P, mode, n, iters, what, **kw):
-    """one checked call on a 0xEE-prefilled rx, then everything a caller can
-    see: no error, every payload checked, the reference's receive count, the
-    host-computed digest, rx byte for byte with its guard, tx untouched"""
-    for r in (0, 1):      # (max: the 1-byte ack of a 0-byte unidir message has its guard too)
-        P.c.fill(P.bufs[r][1], max(n, 1) + GUARD, mpx.FILL_BYTE, payload.GUARD_BYTE)
-    out, errs = P.run(mode, n, iters, **kw)
-    assert not errs, (what, errs)
-    done = O.lib().oracle_nb_waited(iters) if mode == NONBLOCKING else iters
-    for r in (0, 1):
-        t = out[r]
-        expected = P.host[P.peer(r)][:received(mode, r, n)]
-        assert t.check_failures == 0 and t.check_iters == iters, (what, r, t.check_failures, t.check_iters)
-        assert t.recv_done == done, (what, r, t.recv_done)
-        assert t.recv_digest == (done * O.checksum(expected)) & M64, (what, r)
-        assert_region(P.c, P.bufs[r][1], 0, expected, what=f"{what}: rx of rank {r}")
-        # (the whole of tx, not only the n bytes sent: a push that landed in it lands anywhere)
-        payload.compare(P.c.read(P.bufs[r][0], P.cap), P.host[r], 0, f"{what}: tx of rank {r} after the call")
-    return out
 
 
 # --------------------------------------------------------------------------

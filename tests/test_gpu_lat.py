@@ -153,12 +153,17 @@ def test_a_stalled_iteration_is_attributed_to_its_index(pair, monkeypatch):
     """positive control: rank 1's last workgroup stalls 20 ms before pulling
     the call's last payload (MPX_TEST lag_wg), so iteration 19 of 20 — and only
     it — takes >= 20 ms on both sides: rank 1's workgroup 0 waits for that
-    chunk before its send, rank 0 waits for that send"""
+    chunk before its send, rank 0 waits for that send.  The stall is sized
+    in ticks by the library (us x 100), so the tick count alone would pass
+    at any clock rate: the host's own clock must have seen the 20 ms too
+    (less the 2 % of test_kernel_clock_against_events_and_the_host_clock)."""
     P = pair
     monkeypatch.setenv("MPX_TEST", "lag_wg=1:-1:20000")
-    traced(P, mpx.MODE_PINGPONG, B_BULK, 20, True, 64)
+    out = traced(P, mpx.MODE_PINGPONG, B_BULK, 20, True, 64)
     monkeypatch.setenv("MPX_TEST", "")
     for r in (0, 1):
+        print(f"rank {r}: wall_s {out[r].wall_s:.6f} device_s {out[r].device_s:.6f}")
+        assert out[r].wall_s >= 0.0196
         lat, raw = P.c.lat_get(r), P.c.lat_raw(r)
         print(f"rank {r}: max {lat['max_ticks']} ticks at iteration {lat['max_iter']}, "
               f"p50 {mpx.lat_quantile(lat, 0.5)}, deltas {[b - a for a, b in zip(raw, raw[1:])]}")
@@ -167,6 +172,48 @@ def test_a_stalled_iteration_is_attributed_to_its_index(pair, monkeypatch):
         assert lat["max_ticks"] >= 2_000_000
         assert mpx.lat_quantile(lat, 0.5) < lat["max_ticks"]
         assert mpx.lat_quantile(lat, 1.0) == mpx.lat_bucket_floor(mpx.lat_bucket(lat["max_ticks"]))
+
+
+CLOCK_ITERS = 30000
+# t[iters], the recorder's last tick, is read inside the loop, the kTsLoop stamp
+# right after it: the tick's histogram add and raw store and a second clock
+# read lie between.  Measured 20 to 40 ticks (the clock steps by 4) over 16
+# calls of 1 to 30000 iterations on both ranks; allowed ten
+# times the largest
+GAP_MEASURED_TICKS = 40
+GAP_S = 10 * GAP_MEASURED_TICKS * TICK
+
+
+def test_kernel_clock_against_events_and_the_host_clock(pair):
+    """Every kernel-side time is ticks x 1e-8 s (complete_call, mpx_lat.tick_s,
+    the lag knob, the go timeout).  One unarmed 8-byte ping-pong long enough
+    that dispatch and completion (tens of microseconds) are under 0.5 % of
+    it: the kernel's span by its own clock must lie inside the hipEvent
+    bracket of the same kernel and inside the host's CLOCK_MONOTONIC span
+    from the launch, and fill at least 98 % of each — two clocks the project
+    does not scale.  A wrong rate constant is off by a factor of 2 or more.
+    The recorder's figures of the same call tie mpx_lat.tick_s to the same
+    scale: its iterations add up to the kernel's span less the wait for the
+    peer's post and the tail, up to the instructions between the last tick
+    and the kTsLoop stamp."""
+    P = pair
+    out = traced(P, mpx.MODE_PINGPONG, B_LL, CLOCK_ITERS, False, 0, check=False)
+    for r in (0, 1):
+        t, ph, lat = out[r], P.c.phases(r), P.c.lat_get(r)
+        P.c.lat_disable(r)
+        k = ph["kernel_s"]
+        print(f"rank {r}: kernel_s {k:.6f} device_s {t.device_s:.6f} wall_s {t.wall_s:.6f} "
+              f"kernel/device {k / t.device_s:.5f} kernel/wall {k / t.wall_s:.5f}")
+        assert ph["armed"] == 0 and t.wall_s == ph["wall_s"]
+        assert t.device_s >= 0.020, "too short for the 2 % bound: raise CLOCK_ITERS"
+        assert k <= t.device_s and k <= t.wall_s
+        assert k >= 0.98 * t.device_s
+        assert k >= 0.98 * t.wall_s
+        loop_s = k - ph["posted_wait_s"] - ph["tail_s"]
+        gap = loop_s - lat["sum_ticks"] * lat["tick_s"]
+        print(f"rank {r}: loop {loop_s:.9f} s, recorded {lat['sum_ticks']} ticks, gap {gap / TICK:.2f} ticks")
+        assert lat["count"] == CLOCK_ITERS
+        assert -0.5 * TICK <= gap <= GAP_S + 0.5 * TICK
 
 
 def test_other_engines_refuse_the_recorder():

@@ -156,3 +156,94 @@ def test_sub_buffer():
     b = mpx.Buffer(0x7f0000001000, 0, 4096)
     s = payload.sub(b, 48)
     assert (s.ptr, s.dev, s.size) == (b.ptr + 48, 0, 4048)
+
+
+# ---- the wrap points of tests/test_gpu_wrap.py, on the host ------------------
+WRAP_CPP = r"""#include "mpx_internal.h"
+#include <cstdio>
+using namespace mpx;
+int main() {
+    unsigned long long a, b, c;
+    char op[16];
+    while (scanf("%15s %llu %llu %llu", op, &a, &b, &c) == 4) {
+        if (op[0] == 't') printf("%u\n", ll_tag(a));
+        else if (op[0] == 'f') printf("%llu\n", fin_word(a, b, b, b, b, b, b, c));
+        else if (op[0] == 's') printf("%d\n", ring_slots(a, (long long)b));
+        else printf("%d\n", ring_slot((int)a, (int)b, (int)c));
+    }
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def internal(tmp_path_factory):
+    """mpx_internal.h's own host functions, through a host-only program (the
+    way tests/test_abi.py compiles the completion line): lines of "op a b c"
+    in, one number per line out"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    d = tmp_path_factory.mktemp("wrap")
+    (d / "wrap.cpp").write_text(WRAP_CPP)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I",
+                    os.path.join(mpx.PKG_ROOT, "csrc"), str(d / "wrap.cpp"), "-o", str(d / "wrap")],
+                   check=True, capture_output=True)
+
+    def ask(rows):
+        text = "".join(f"{op} {a} {b} {c}\n" for op, a, b, c in rows)
+        out = subprocess.run([str(d / "wrap")], input=text, check=True, capture_output=True, text=True).stdout.split()
+        assert len(out) == len(rows)
+        return [int(x) for x in out]
+    return ask
+
+
+P31, P32 = 1 << 31, 1 << 32
+
+
+def test_ll_tag_is_never_zero_and_wraps_at_2_31_exactly(internal):
+    """ll_tag's contract (mpx_internal.h): never 0, so a zeroed mailbox never
+    matches; distinct for pushes 1 .. 2^31 - 1 apart; EQUAL at a distance of
+    exactly 2^31 — the documented bound, which
+    tests/test_gpu_wrap.py is written around"""
+    bases = [1, 2, P31 - 4, P31 - 1, P31, P31 + 1, P32 - 4, P32 - 1, P32, P32 + 1, 3 * P31 - 1, (1 << 63) + 5,
+             (1 << 64) - P31 - 1]
+    near = [1, 2, 3, 4, 8, 9, 255, 256, (1 << 16), (1 << 30), P31 - 2, P31 - 1]
+    rows = [("t", s, 0, 0) for s in bases] + [("t", s + d, 0, 0) for s in bases for d in near + [P31]]
+    tags = internal(rows)
+    assert all(0x80000000 <= t <= 0xFFFFFFFF for t in tags)
+    base, rest = tags[:len(bases)], tags[len(bases):]
+    for k, s in enumerate(bases):
+        mine = rest[k * (len(near) + 1):(k + 1) * (len(near) + 1)]
+        assert all(t != base[k] for t in mine[:-1]), s
+        assert mine[-1] == base[k], s
+        assert len(set(mine[:-1])) == len(near), s
+    # the run the GPU cases cross: pushes 2^31 - 1, 2^31, 2^31 + 1, and push 1
+    assert internal([("t", P31 - 1, 0, 0), ("t", P31, 0, 0), ("t", P31 + 1, 0, 0), ("t", 1, 0, 0)]) == [
+        0xFFFFFFFF, 0x80000000, 0x80000001, 0x80000001]
+
+
+def test_a_cleared_completion_line_is_never_a_sealed_one(internal):
+    """tokens 2^32 and 2^33 have a low word of 0, like the line launch_call
+    clears: the seal of seven zero fields is not 0, so fin_sealed rejects the
+    cleared line (and any all-equal line the test tries)"""
+    for token in (P32, 2 * P32, 3 * P32):
+        words = internal([("f", token, v, v) for v in (0, 1, token)])
+        assert all(w != 0 and w & 0xFFFFFFFF == 0 and w >> 32 != 0 for w in words), (token, words)
+        assert len(set(words)) == 3
+
+
+def test_ring_arithmetic_is_the_librarys(internal):
+    """payload.ring_slots / ring_slot restate mpx_internal.h; the credit case
+    of tests/test_gpu_wrap.py (three slots for 4097-byte messages) rests on
+    them and on ring_bytes_for"""
+    cases = [(0, 4097), (8322, 4097), (8193, 4097), (12291, 4097), (64 << 20, 1), (64 << 20, 0), (255 * 4161, 4097)]
+    assert internal([("s", rb, n, 0) for rb, n in cases]) == [payload.ring_slots(rb, n) for rb, n in cases]
+    assert payload.ring_slots(payload.ring_bytes_for(4097 + payload.GUARD, 2 * (4097 + payload.GUARD)), 4097) == 3
+    assert payload.ring_bytes_for(4161, 0) == 0 and payload.ring_bytes_for(4161) == 255 * 4161
+    assert payload.ring_bytes_for(1 << 20) == 64 << 20
+    # 20 receives in 3 slots: the last lands in rx (slot 0), each slot is reused
+    slots = internal([("r", j, 20, 3) for j in range(20)])
+    assert slots == [(19 - j) % 3 for j in range(20)] and slots[-1] == 0
