@@ -111,7 +111,7 @@ typedef struct mpx_timing {
                                  next copy's loads in flight (k_copy_pipe),
                                  7 = bulk payloads pulled by the receiver
                                  (MPX_XFER_PULL), 8 = the SDMA engine's
-                                 pulled form                                    */
+                                 pulled form, 9 = fan exchange (mpx_xfer_fan)   */
     int32_t check_failures;   /* iterations whose payload checksum mismatched  */
     uint64_t check_iters;     /* iterations whose payload was checksummed      */
     /* receive accounting, as the reference's loop completes receives: every
@@ -279,6 +279,67 @@ int mpx_xfer(mpx_ctx *ctx, int mode, int my_group, int my_rank, int peer_rank, i
 /* same, with options (checksum mode, timeouts) and full timing */
 int mpx_xfer_ex(mpx_ctx *ctx, int mode, int my_group, int my_rank, int peer_rank, int iters,
                 void *tx, void *rx, int buff_len, const mpx_xfer_opts *opts, mpx_timing *t);
+
+/* ---- fan exchange: one rank with several peers in one launch --------------- */
+/* mpx_xfer_ex is pairwise, and a rank runs one call at a time.  A fan call of
+   rank my_rank names a set of peers (1 <= npeers <= nranks - 1, distinct,
+   never my_rank, each attached or imported) and exchanges one block with
+   every one of them in ONE kernel launch: MPI_Isend + MPI_Irecv to every
+   peer, then MPI_Waitall.  The job's peer sets must be symmetric (p lists r
+   iff r lists p); each rank may list its peers in any order.
+     Layout: MPI_Alltoall's blocks inside the attached tx / rx — block j at
+   byte offset j * stride, block_len bytes each.  Every iteration pushes
+   tx[p * stride : + block_len) into rx_p[my_rank * stride : ...) for each
+   peer p.  No other byte of rx is written (the stride - block_len gap after
+   a block, the rank's own block and the blocks of ranks outside the set
+   stay), and tx is only read.
+     Per link it is the non-blocking loop without its 256-slot window: `iters`
+   bulk pushes (no LL path), flags on the same publish schedule, every
+   receive counted (recv_done = iters per link); no iteration of one link
+   waits for another link.  Check mode checksums every received block chunk
+   by chunk, poisons all but the last, and paces the sender with per-chunk
+   credits.  The call returns once all `iters` blocks of every peer landed.
+     Kernel engine only (MPX_ERR_UNSUPPORTED otherwise).  MPX_ERR_INVALID,
+   before any GPU work: NULL ctx / peers / t, a bad peer list, stride not a
+   multiple of 16 or below block_len, (max rank involved + 1) * stride past
+   my_rank's attached length or (my_rank + 1) * stride past a peer's, flags
+   other than MPX_XFER_STREAM, a grid (the sum of the links' widths) above
+   256.  MPX_ERR_STATE: my_rank holds an armed call or timed out before.
+     Width of a link: opts.nwg, else the environment's MPX_FAN_WG, else
+   min(the pair rule, max(1, 128 / (nranks - 1))); then at least 1 KiB per
+   workgroup.  Only things both ends see alike go in, so they agree.
+     Timing: bytes = 2 * block_len * iters * npeers, launches = 1, nwg = the
+   widest link, protocol = 9, recv_done = npeers * iters; recv_digest,
+   check_iters and check_failures are summed over the links.  The link
+   counters (mpx_link_counters) move as if each link had run a pair call.
+   Fan calls are never traced by the latency recorder.  The ABI version is
+   unchanged: callers detect the feature by symbol. */
+typedef struct mpx_fan_opts {
+    int32_t check;            /* 1: checksum + poison every received block     */
+    int32_t flags;            /* 0 or MPX_XFER_STREAM                          */
+    uint32_t timeout_ms;      /* per-wait device deadline; 0 = default (10 s)  */
+    int32_t nwg;              /* width of every link; 0 = automatic            */
+    const uint64_t *expect_checksum; /* [npeers], check = 1: mpx_checksum() of
+                                 peer k's tx block for my_rank                 */
+} mpx_fan_opts;
+typedef struct mpx_fan_link {
+    int32_t peer;             /* peers[k]                                      */
+    int32_t nwg;              /* the link's width                              */
+    uint64_t recv_done;       /* receives completed on the link                */
+    uint64_t recv_digest;     /* check mode: sum of their checksums            */
+    int32_t check_failures;   /* receives whose checksum mismatched            */
+    int32_t pad;
+    double device_s;          /* kernel entry -> the link's last workgroup's
+                                 end (the kernel's clock, 10 ns ticks)         */
+} mpx_fan_link;
+int mpx_xfer_fan(mpx_ctx *ctx, int my_rank, int npeers, const int *peers, int iters, void *tx, void *rx,
+                 int block_len, size_t stride, const mpx_fan_opts *opts, mpx_timing *t,
+                 mpx_fan_link *links /* [npeers] or NULL */);
+/* The width mpx_xfer_fan gives a link of block_len bytes in a context of
+   nranks ranks (same_device: both ranks on one GPU; nwg: mpx_fan_opts.nwg),
+   MPX_FAN_WG included; -1 for arguments the call would refuse.  Pure host
+   arithmetic: no GPU, no context. */
+int mpx_fan_width(int nranks, int block_len, int same_device, int nwg);
 
 /* Arm the next transfer of my_rank (kernel engine): its kernel is launched
    now and waits on the device; the next mpx_xfer_ex with the SAME arguments

@@ -21,7 +21,7 @@ constexpr int kStageMaxBytes = 60 << 10; // LDS-staged tx chunk per workgroup, m
 
 // Protocol ids reported in mpx_timing.protocol
 enum Proto { kProtoLL = 0, kProtoBulk = 1, kProtoSdma = 2, kProtoRccl = 3, kProtoCopy = 4, kProtoCopySteps = 5,
-             kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8 };
+             kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8, kProtoFan = 9 };
 
 // One rank's receive mailbox, in that rank's HBM (uncached / fine-grained so a
 // poll sees stores that arrive over xGMI).  Written ONLY by the peers, polled
@@ -242,7 +242,93 @@ inline int bulk_nwg(long long len, bool same_device) {
     return (int)n;
 }
 
+// ---- fan exchange (mpx_xfer_fan, k_xfer_fan) --------------------------------
+// One rank exchanges a block with each of several peers in ONE launch: the
+// grid is the sum of the links' widths, and workgroup (k, w) pushes, receives
+// and (check mode) checks chunk w of link k on its own.
+//
+// One record per link, in the rank's device memory, written by the host
+// before the launch (on the rank's stream) and read back after it.
+struct FanLink {
+    unsigned char* peer_rx;   // where this rank's block lands: the peer's rx + my_rank * stride
+    Mailbox* peer_mb;         // the peer's mailbox (written)
+    u64 tx_seq0, rx_seq0;     // the link's push numbers before the call
+    u64 call;                 // number of this call on the link (Mailbox.posted)
+    long long off;            // peer * stride: the link's block in this rank's own tx and rx
+    int peer;                 // the peer's rank = its slot in this rank's mailbox
+    int nwg;                  // the link's width (the same on both sides)
+    int csum0;                // k * iters: the link's first word of the checksum array
+    int pad;
+    // results, device atomics of the link's workgroups (host: ~0 and 0)
+    u64 recv_done;            // min over the link's chunks of the receives completed
+    u64 t_end;                // max over the link's workgroups of now_ticks() at their end
+};
+constexpr int kFanMaxGrid = 256;   // one rank's fan grid, at most (DESIGN.md "Fan exchange")
+// the rank's fan table: the link records, then blockIdx.x -> link << 16 | w
+struct FanTable {
+    FanLink link[MPX_MAX_RANKS];
+    unsigned map[kFanMaxGrid];
+};
+struct FanArgs {
+    const unsigned char* tx;
+    unsigned char* rx;
+    Mailbox* my_mb;
+    Status* status;
+    u64* csum;                // [nlinks * iters] raw checksum sums (check mode)
+    u64* gbar;                // the rank's scratch words
+    FanTable* tab;
+    u64 timeout_ticks;
+    u64 done_token;
+    long long len;            // block_len
+    int iters, nlinks, my_slot;
+    int check, stream, nb_publish, skip_push;
+};
+
+// Default width of a fan link: the pair rule, capped so that the kernels of
+// nranks ranks sharing one GPU (each up to nranks - 1 links wide) stay
+// resident together.  Only things both ends of a link see alike go in.
+inline int fan_default_nwg(long long block_len, bool same_device, int nranks) {
+    const int share = nranks > 1 ? 128 / (nranks - 1) : 128;
+    const int cap = share < 1 ? 1 : share;
+    const int n = bulk_nwg(block_len, same_device);
+    return n < cap ? n : cap;
+}
+// at least kMinPushChunk bytes per workgroup, at least one workgroup
+inline int fan_narrow_nwg(int nwg, long long block_len) {
+    const long long most = (block_len + kMinPushChunk - 1) / kMinPushChunk;
+    const long long n = nwg < most ? nwg : most;
+    return n < 1 ? 1 : (int)n;
+}
+
+// Fills the host image of a rank's fan table for a call whose links have the
+// given widths: the records' widths and checksum offsets and the workgroup
+// map, links interleaved over consecutive block indices (workgroup w of every
+// link, then w + 1 of every link that wide).  Returns the grid, or -1 if it
+// exceeds kFanMaxGrid or a width is out of range.  Pure host arithmetic
+// (tools/fan_host_check.cpp runs it under the host sanitizers).
+inline int fan_build_map(FanTable* tab, int nlinks, const int* nwg, int iters) {
+    if (nlinks < 1 || nlinks > MPX_MAX_RANKS) return -1;
+    long long grid = 0;
+    int widest = 0;
+    for (int k = 0; k < nlinks; ++k) {
+        if (nwg[k] < 1 || nwg[k] > kMaxPushWG) return -1;
+        grid += nwg[k];
+        if (nwg[k] > widest) widest = nwg[k];
+    }
+    if (grid > kFanMaxGrid) return -1;
+    int b = 0;
+    for (int w = 0; w < widest; ++w)
+        for (int k = 0; k < nlinks; ++k)
+            if (w < nwg[k]) tab->map[b++] = ((unsigned)k << 16) | (unsigned)w;
+    for (int k = 0; k < nlinks; ++k) {
+        tab->link[k].nwg = nwg[k];
+        tab->link[k].csum0 = k * iters;
+    }
+    return b;
+}
+
 // Launchers implemented in mpx_kernels.hip
+hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s);
 hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s);
 hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out);
 // all `iters` copies in one launch with a grid barrier between steps; *bar

@@ -6,6 +6,8 @@
 //               per rank: pushes go straight into the peer's HBM over xGMI,
 //               receives are device-side polls of the rank's mailbox
 //               (do_mpi_benchmark*, /root/reference/mpi_perf.c:66-145)
+//   k_xfer_fan  one rank's blocks to and from several peers in one launch
+//               (mpx_xfer_fan): every workgroup owns one chunk of one link
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -1616,6 +1618,177 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull_lat(XferArgs a) {
     xfer_pull_body<MODE, GROUP, true>(a);
 }
 
+// ---------------------------------------------------------------------------
+// k_xfer_fan: one rank's side of a fan exchange (mpx_xfer_fan) — a block to
+// and from each of several peers in ONE launch.  The grid is the sum of the
+// links' widths; workgroup (k, w) (FanTable.map) owns chunk w of link k and
+// runs that chunk's whole loop alone: no workgroup waits for another link.
+//   * post: workgroup (k, 0) stores this call's number into peer k's mailbox
+//     (Mailbox.posted); nothing is pushed to a peer before its post was seen;
+//   * push: chunk w of tx block peers[k] into the peer's rx block of this
+//     rank — 16-B sc0|sc1 buffer stores (push_units), tx read from HBM/L2
+//     (every peer gets another block: no LDS staging) — then, on the
+//     non-blocking loop's publish schedule, drain + flag[me][w];
+//   * receive: without check mode only the link's last flag of chunk w is
+//     waited for; in check mode chunk w of every receive is checksummed and
+//     poisoned (all but the last) and credit[me][w] returned to the sender,
+//     whose workgroup w pushes iteration i >= 1 only after the credit of
+//     i - 1 (else the poison could land on a payload that arrived early);
+//   * end of the link: min of the receives completed and max of the end time
+//     over the link's workgroups (device atomics into the link's record).
+// An empty chunk (lo >= n) moves nothing and still publishes, credits and
+// counts.  Every wait is bounded (should_stop / give_up).  The call ends as
+// every kernel-engine call does (last_to_finish, finish_last): scratch words
+// back to zero, one sealed Fin line.
+// ---------------------------------------------------------------------------
+// CHECK: check mode's kernel (a call's f.check picks the instantiation, so the
+// plain loop carries none of the checking code's registers).  Plain: 48 VGPRs,
+// 67 SGPRs; check: 73 VGPRs, 78 SGPRs under amdgpu_num_sgpr(80) — left alone
+// the compiler takes 106 SGPRs there, as for every k_xfer kernel; with the
+// cap it keeps 38 scalar values in VGPR lanes instead.  No scratch either way
+// (DESIGN.md "Fan exchange").
+template <bool CHECK>
+__global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan(FanArgs f) {
+    __shared__ int s_abort;
+    __shared__ u64 lds4[4];
+    if (threadIdx.x == 0) s_abort = 0;
+    XferArgs x{};   // what the shared wait, push and end-of-call helpers read
+    x.status = f.status;
+    x.gbar = f.gbar;
+    x.timeout_ticks = f.timeout_ticks;
+    x.done_token = f.done_token;
+    x.stream = f.stream;
+    x.iters = f.iters;
+    Loop<MPX_MODE_NONBLOCKING> L{x, &s_abort, lds4, nullptr, {}};
+    __syncthreads();
+    L.stamp(kTsEntry);
+    const unsigned m = f.tab->map[blockIdx.x];
+    const int k = (int)(m >> 16), w = (int)(m & 0xffffu);
+    FanLink& lk = f.tab->link[k];
+    const long long n = f.len;
+    const int nw = lk.nwg;
+    const u64 tx0 = lk.tx_seq0, rx0 = lk.rx_seq0;
+    // this workgroup's chunk [lo, hi) of the link's block (Loop::chunk_of)
+    const long long chunk = (((n + nw - 1) / nw) + 15) & ~15ll;
+    const long long lo = (long long)w * chunk;
+    const long long hi = lo + chunk < n ? lo + chunk : n;
+    const unsigned bytes = lo < hi ? (unsigned)(hi - lo) : 0u;
+    const int nv = (int)(bytes >> 4);
+    const unsigned tail = bytes & 15;
+    const long long at = bytes ? lk.off + lo : 0;       // (an empty chunk touches no memory)
+    const unsigned char* src = f.tx + at;
+    const __amdgpu_buffer_rsrc_t dst = rsrc(lk.peer_rx + (bytes ? lo : 0), bytes);
+    const __amdgpu_buffer_rsrc_t mine = rsrc(f.rx + at, bytes);
+    u64* flag_out = &lk.peer_mb->flag[f.my_slot][w];
+    u64* credit_out = &lk.peer_mb->credit[f.my_slot][w];
+    const u64* flag_in = &f.my_mb->flag[lk.peer][w];
+    const u64* credit_in = &f.my_mb->credit[lk.peer][w];
+
+    // bounded one-lane poll of a word a peer writes
+    auto wait_ge = [&](const u64* p, u64 want, int iter) -> bool {
+        if (threadIdx.x == 0) {
+            const u64 t0 = now_ticks();
+            u64 spins = 0;
+            while (ld_sys(p) < want) {
+                if (L.should_stop(++spins, t0)) { L.give_up(iter); break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        __syncthreads();
+        return !L.aborted();
+    };
+
+    if (w == 0 && threadIdx.x == 0) st_sys(&lk.peer_mb->posted[f.my_slot], lk.call);
+    bool ok = f.iters == 0 || wait_ge(&f.my_mb->posted[lk.peer], lk.call, 0);
+    L.stamp(kTsPosted);
+    u64 done = 0;
+    for (int i = 0; ok && i < f.iters; ++i) {
+        if (CHECK && i > 0) {                        // chunk w of push i - 1 was checked: its poison is in
+            ok = wait_ge(credit_in, tx0 + (u64)i, i);
+            if (!ok) break;
+        }
+        if (bytes && f.skip_push != i + 1) {           // (test knob: this payload is "lost")
+            L.push_units_aux<false>(reinterpret_cast<const v4u*>(src), dst, nv);
+            if (threadIdx.x < tail) {
+                const unsigned o = (unsigned)nv * 16 + threadIdx.x;
+                __builtin_amdgcn_raw_buffer_store_b8(src[o], dst, o, 0, kAuxSys);
+            }
+        }
+        if (CHECK || (i + 1) % f.nb_publish == 0 || i + 1 == f.iters) {
+            drain_stores();                            // every storing wave
+            __syncthreads();
+            if (threadIdx.x == 0) st_sys(flag_out, tx0 + (u64)i + 1);
+        }
+        if constexpr (CHECK) {
+        ok = wait_ge(flag_in, rx0 + (u64)i + 1, i);
+        if (!ok) break;
+        // checksum (word indices count from the block's start) and poison
+        // this chunk of receive i, as Loop::sum_chunk does for a pair's
+        const bool keep = i + 1 == f.iters;
+        const u64 poison = 0x5a5a5a5a5a5a5a5aull ^ (u64)i;
+        u64 acc = 0;
+        if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        drain_stores();
+        __syncthreads();
+        if (bytes) {
+            const v4u pv = {(unsigned)poison, (unsigned)(poison >> 32), (unsigned)poison, (unsigned)(poison >> 32)};
+            for (int v = threadIdx.x; v < nv; v += kBlock) {
+                const v4u q = __builtin_amdgcn_raw_buffer_load_b128(mine, v * 16, 0, kAuxSys);
+                const u64 kw = (u64)(lo / 8) + 2 * (u64)v;
+                acc += csum_term(((u64)q.y << 32) | q.x, kw);
+                acc += csum_term(((u64)q.w << 32) | q.z, kw + 1);
+                if (!keep) __builtin_amdgcn_raw_buffer_store_b128(pv, mine, v * 16, 0, kAuxSys);
+            }
+            if (threadIdx.x < 2 && 8 * threadIdx.x < tail) {   // only the block's last chunk has a tail
+                const unsigned o = (unsigned)nv * 16 + 8 * threadIdx.x;
+                u64 word = 0;
+                for (unsigned b = 0; b < 8 && o + b < bytes; ++b)
+                    word |= (u64)__builtin_amdgcn_raw_buffer_load_b8(mine, o + b, 0, kAuxSys) << (8 * b);
+                acc += csum_term(word, (u64)(lo + o) / 8);
+            }
+            __syncthreads();
+            if (!keep && threadIdx.x < tail)
+                __builtin_amdgcn_raw_buffer_store_b8((unsigned char)poison, mine, (unsigned)nv * 16 + threadIdx.x, 0,
+                                                     kAuxSys);
+        }
+        drain_stores();                                // the poison is in before the credit goes
+        const u64 s = block_sum(acc, lds4);
+        if (threadIdx.x == 0) {
+            if (s) atomicAdd(&f.csum[lk.csum0 + i], s);
+            st_sys(credit_out, rx0 + (u64)i + 1);
+        }
+        ++done;
+        }
+    }
+    L.stamp(kTsLoop);
+    // Waitall: without check mode, the link's last flag of this chunk
+    if (!CHECK && ok && f.iters > 0 && wait_ge(flag_in, rx0 + (u64)f.iters, f.iters - 1)) done = (u64)f.iters;
+    drain_stores();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_fetch_min(&lk.recv_done, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&lk.t_end, now_ticks(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!L.last_to_finish()) return;
+    // workgroup 0, every other workgroup done: the call's receive count and
+    // digest (of a call that completed: a timeout fails it anyway)
+    u64 part = 0, dpart = 0;
+    for (int j = threadIdx.x; j < f.nlinks; j += kBlock)
+        part += __hip_atomic_load(&f.tab->link[j].recv_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CHECK && !__hip_atomic_load(&f.gbar[kScrAbort], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        const u64 fmix = mix64((u64)n);
+        for (int j = threadIdx.x; j < f.nlinks * f.iters; j += kBlock)
+            dpart += __hip_atomic_load(&f.csum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ fmix;
+    }
+    const u64 d = block_sum(part, lds4);
+    const u64 g = block_sum(dpart, lds4);
+    if (threadIdx.x == 0) {
+        L.rdone = d;
+        L.rdig = g;
+    }
+    L.finish_last();
+}
+
 // stream engines' receive accounting (launch_account)
 __global__ __launch_bounds__(kBlock) void k_account(Status* st, const u64* csum, int j0, int count, u64 fmix) {
     __shared__ u64 lds4[4];
@@ -1670,6 +1843,14 @@ hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (unsigned)a.stage, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s) {
+    if (grid < 1 || grid > kFanMaxGrid) return hipErrorInvalidValue;
+    (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
+    void (*k)(FanArgs) = a.check ? k_xfer_fan<true> : k_xfer_fan<false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -239,6 +239,8 @@ struct Rank {
     int lat_alloc = 0;             //   raw_cap the block was allocated for
     int lat_cap = 0;               //   raw_cap in force
     bool lat_on = false;           //   blocking calls of this rank are traced
+    FanTable* fan_tab = nullptr;   // fan exchange (mpx_xfer_fan): the link table in device memory
+    FanTable* fan_host = nullptr;  //   and its pinned host image (allocated on the first fan call)
     u64 tx_seq[MPX_MAX_RANKS] = {};
     u64 rx_seq[MPX_MAX_RANKS] = {};
     u64 calls[MPX_MAX_RANKS] = {};   // transfer calls on the link to that rank (Mailbox.posted)
@@ -707,10 +709,11 @@ bool pull_requested(const mpx_xfer_opts* o) {
     return (o && (o->flags & MPX_XFER_PULL)) || env_pull;
 }
 
-u64 timeout_ticks(const mpx_xfer_opts* o) {
-    const u64 ms = (o && o->timeout_ms) ? o->timeout_ms : 10000;
+u64 timeout_ticks_ms(uint32_t timeout_ms) {
+    const u64 ms = timeout_ms ? timeout_ms : 10000;
     return ms * 100000ull;   // s_memrealtime runs at 100 MHz
 }
+u64 timeout_ticks(const mpx_xfer_opts* o) { return timeout_ticks_ms(o ? o->timeout_ms : 0); }
 
 // ---------------------------------------------------------------------------
 // engine: kernel
@@ -1656,6 +1659,8 @@ int mpx_finalize(mpx_ctx* ctx) {
         if (rk.scratch) (void)hipFree(rk.scratch);
         if (rk.csum) (void)hipFree(rk.csum);
         if (rk.lat) (void)hipFree(rk.lat);
+        if (rk.fan_tab) (void)hipFree(rk.fan_tab);
+        if (rk.fan_host) (void)hipHostFree(rk.fan_host);
         for (void* q : rk.retired) (void)hipFree(q);
         if (rk.status) (void)hipHostFree(rk.status);
     }
@@ -1897,6 +1902,8 @@ void release_rank(Rank& rk) {
     if (rk.scratch) (void)hipFree(rk.scratch);
     if (rk.csum) (void)hipFree(rk.csum);
     if (rk.lat) (void)hipFree(rk.lat);
+    if (rk.fan_tab) (void)hipFree(rk.fan_tab);
+    if (rk.fan_host) (void)hipHostFree(rk.fan_host);
     for (void* q : rk.retired) (void)hipFree(q);
     if (rk.status) (void)hipHostFree(rk.status);
     rk.ev0.reset();
@@ -2209,6 +2216,260 @@ int mpx_xfer_ex(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank
     }
     if (st != MPX_OK) return st;
     return finish_xfer(me, mode, my_group, my_rank, iters, buff_len, opts, t);
+}
+
+// ---------------------------------------------------------------------------
+// fan exchange (include/mpx.h mpx_xfer_fan; k_xfer_fan)
+// ---------------------------------------------------------------------------
+namespace {
+// MPX_FAN_WG: every link's width (read per call; every rank of a job inherits
+// the same environment, so both sides of a link agree)
+int fan_env_nwg() {
+    const char* v = getenv("MPX_FAN_WG");
+    return v ? atoi(v) : 0;
+}
+
+// The width of one fan link: the call's option, else MPX_FAN_WG, else the
+// default rule; then at least kMinPushChunk bytes per workgroup.  0: invalid.
+int fan_link_nwg(int nwg_opt, long long block_len, bool same_dev, int nranks) {
+    const int env = fan_env_nwg();
+    const int w = nwg_opt > 0 ? nwg_opt : env > 0 ? env : fan_default_nwg(block_len, same_dev, nranks);
+    if (w > kMaxPushWG) return 0;
+    return fan_narrow_nwg(w, block_len);
+}
+
+// The rank's fan table: device memory the kernel reads and folds its link
+// results into, and its pinned host image (allocated on the first fan call;
+// hipMalloc, unlike hipFree, does not wait for other ranks' kernels).
+int ensure_fan_table(Rank& me) {
+    if (me.fan_tab) return MPX_OK;
+    void* h = nullptr;
+    HIPCK(hipHostMalloc(&h, sizeof(FanTable), hipHostMallocDefault));
+    void* d = nullptr;
+    const hipError_t e = hipMalloc(&d, sizeof(FanTable));
+    if (e != hipSuccess) {
+        (void)hipHostFree(h);
+        HIPCK(e);
+    }
+    me.fan_host = static_cast<FanTable*>(h);
+    me.fan_tab = static_cast<FanTable*>(d);
+    return MPX_OK;
+}
+}  // namespace
+
+int mpx_fan_width(int nranks, int block_len, int same_device, int nwg) {
+    if (nranks < 2 || nranks > MPX_MAX_RANKS || block_len < 0 || nwg < 0) return -1;
+    const int w = fan_link_nwg(nwg, block_len, same_device != 0, nranks);
+    return w > 0 ? w : -1;
+}
+
+int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int iters, void* tx, void* rx,
+                 int block_len, size_t stride, const mpx_fan_opts* opts, mpx_timing* t, mpx_fan_link* links) {
+    if (!ctx || !peers || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    const double t_call = now_s();
+    // ---- argument checks: all before any GPU work ---------------------------
+    if (my_rank < 0 || my_rank >= ctx->nranks) return fail(MPX_ERR_INVALID, "rank %d", my_rank);
+    if (npeers < 1 || npeers > ctx->nranks - 1)
+        return fail(MPX_ERR_INVALID, "npeers %d not in [1, %d]", npeers, ctx->nranks - 1);
+    if (links) memset(links, 0, (size_t)npeers * sizeof *links);
+    if (iters < 0 || block_len < 0) return fail(MPX_ERR_INVALID, "iters %d, block_len %d", iters, block_len);
+    if ((long long)npeers * iters > 0x7fffffffll) return fail(MPX_ERR_INVALID, "npeers x iters %d x %d", npeers, iters);
+    if (stride % 16 != 0 || stride < (size_t)block_len)
+        return fail(MPX_ERR_INVALID, "stride %zu: a multiple of 16, at least block_len %d", stride, block_len);
+    if (opts && (opts->flags & ~MPX_XFER_STREAM)) return fail(MPX_ERR_INVALID, "flags %#x: only MPX_XFER_STREAM", opts->flags);
+    const bool check = opts && opts->check;
+    if (check && !opts->expect_checksum) return fail(MPX_ERR_INVALID, "check mode needs expect_checksum[npeers]");
+    bool seen[MPX_MAX_RANKS] = {};
+    int top = my_rank;
+    for (int k = 0; k < npeers; ++k) {
+        const int p = peers[k];
+        if (p < 0 || p >= ctx->nranks) return fail(MPX_ERR_INVALID, "peer rank %d", p);
+        if (p == my_rank) return fail(MPX_ERR_INVALID, "rank %d lists itself as a peer", my_rank);
+        if (seen[p]) return fail(MPX_ERR_INVALID, "peer rank %d listed twice", p);
+        seen[p] = true;
+        if (p > top) top = p;
+    }
+    if (ctx->engine != MPX_ENGINE_KERNEL) return fail(MPX_ERR_UNSUPPORTED, "mpx_xfer_fan: the kernel engine only");
+    Rank& me = ctx->r[my_rank];
+    if (!me.local) return fail(MPX_ERR_STATE, "rank %d is not attached in this process", my_rank);
+    if (me.broken) return fail(MPX_ERR_STATE, "rank %d: a previous transfer timed out", my_rank);
+    if (me.armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", my_rank);
+    if (tx != me.tx || rx != me.rx) return fail(MPX_ERR_INVALID, "tx/rx are not rank %d's attached buffers", my_rank);
+    if ((size_t)(top + 1) * stride > me.len)
+        return fail(MPX_ERR_INVALID, "block %d at stride %zu lies past rank %d's attached length %zu", top, stride, my_rank,
+                    me.len);
+    int nwg[MPX_MAX_RANKS];
+    for (int k = 0; k < npeers; ++k) {
+        const Rank& peer = ctx->r[peers[k]];
+        if (!peer.local && !peer.imported)
+            return fail(MPX_ERR_STATE, "peer rank %d is unknown (attach or import it)", peers[k]);
+        if ((size_t)(my_rank + 1) * stride > peer.len)
+            return fail(MPX_ERR_INVALID, "block %d at stride %zu lies past rank %d's attached length %zu", my_rank, stride,
+                        peers[k], peer.len);
+        nwg[k] = fan_link_nwg(opts ? opts->nwg : 0, block_len, same_device(me, peer), ctx->nranks);
+        if (nwg[k] < 1) return fail(MPX_ERR_INVALID, "nwg > %d", kMaxPushWG);
+    }
+    std::vector<FanTable> image(1);
+    FanTable& ht = image[0];
+    memset(&ht, 0, sizeof ht);
+    const int grid = fan_build_map(&ht, npeers, nwg, iters);
+    if (grid < 0) {
+        long long sum = 0;
+        for (int k = 0; k < npeers; ++k) sum += nwg[k];
+        return fail(MPX_ERR_INVALID, "rank %d: a fan grid of %lld workgroups exceeds %d (narrow the links: nwg, MPX_FAN_WG)",
+                    my_rank, sum, kFanMaxGrid);
+    }
+    // ---- set-up ----------------------------------------------------------------
+    DeviceGuard g(me.dev);
+    HIPCK(g.err);
+    TRY(ensure_fan_table(me));
+    const size_t nsum = (size_t)npeers * (size_t)iters;
+    if (check) TRY(ensure_csum(me, (int)nsum));
+    const TestKnobs knobs = test_knobs();
+    FanArgs a{};
+    a.tx = me.tx;
+    a.rx = me.rx;
+    a.my_mb = me.mb;
+    a.status = me.status;
+    a.csum = me.csum;
+    a.gbar = me.scratch;
+    a.tab = me.fan_tab;
+    a.timeout_ticks = timeout_ticks_ms(opts ? opts->timeout_ms : 0);
+    a.len = block_len;
+    a.iters = iters;
+    a.nlinks = npeers;
+    a.my_slot = my_rank;
+    a.check = check ? 1 : 0;
+    a.stream = (opts && (opts->flags & MPX_XFER_STREAM)) ? 1 : 0;
+    a.nb_publish = nb_publish();
+    a.skip_push = knobs.skip_push;
+    // the call's numbers: the rank's token, and a call number on every link
+    // (a call that moves nothing posts nothing new, as for a pair)
+    a.done_token = ++me.token;
+    const bool took_call = iters > 0;
+    int widest = 0;
+    for (int k = 0; k < npeers; ++k) {
+        const int p = peers[k];
+        const Rank& peer = ctx->r[p];
+        FanLink& l = ht.link[k];
+        l.peer_rx = peer.rx + (size_t)my_rank * stride;
+        l.peer_mb = peer.mb;
+        l.tx_seq0 = me.tx_seq[p];
+        l.rx_seq0 = me.rx_seq[p];
+        l.call = took_call ? ++me.calls[p] : me.calls[p];
+        if (knobs.no_posted) l.call = 0;
+        l.off = (long long)((size_t)p * stride);
+        l.peer = p;
+        l.recv_done = ~0ull;
+        l.t_end = 0;
+        if (nwg[k] > widest) widest = nwg[k];
+    }
+    // ---- launch ----------------------------------------------------------------
+    // A call that fails before its kernel is enqueued gives its numbers back
+    // (unprepare_call's rule); once enqueued they stay taken.
+    bool launched = false;
+    double t0 = 0;
+    auto launch = [&]() -> int {
+        if (knobs.fail_launch == my_rank)
+            return fail(MPX_ERR_HIP, "rank %d: launch failed (MPX_TEST fail_launch)", my_rank);
+        memcpy(me.fan_host, &ht, sizeof ht);
+        t0 = now_s();
+        HIPCK(hipMemcpyAsync(me.fan_tab, me.fan_host, sizeof(FanTable), hipMemcpyHostToDevice, me.stream));
+        if (check && nsum) HIPCK(hipMemsetAsync(me.csum, 0, nsum * sizeof(u64), me.stream));
+        me.status->err = 0;
+        me.status->where = 0;
+        memset(&me.status->fin, 0, sizeof(Fin));
+        HIPCK(hipEventRecord(me.ev0, me.stream));
+        HIPCK(launch_fan(a, grid, me.stream));
+        launched = true;
+        HIPCK(hipEventRecord(me.ev1, me.stream));
+        return MPX_OK;
+    };
+    const int lst = launch();
+    if (lst != MPX_OK) {
+        if (!launched) {
+            if (took_call)
+                for (int k = 0; k < npeers; ++k) --me.calls[peers[k]];
+            --me.token;
+        }
+        return lst;
+    }
+    // ---- completion -------------------------------------------------------------
+    double t_done = 0;
+    TRY(wait_kernel(me, a.done_token, false, &t_done));
+    const double t_end = now_s();
+    t->wall_s = t_end - t0;
+    Fin fin{};
+    if (!fin_sealed(me, a.done_token, &fin))
+        return fail(MPX_ERR_HIP, "rank %d: the fan kernel left no completion line", my_rank);
+    float ms = 0;
+    HIPCK(hipEventElapsedTime(&ms, me.ev0, me.ev1));
+    t->device_s = ms * 1e-3;
+    t->bytes = 2ull * (uint64_t)block_len * (uint64_t)iters * (uint64_t)npeers;
+    t->launches = 1;
+    t->nwg = widest;
+    t->protocol = kProtoFan;
+    t->recv_done = fin.recv_done;
+    t->recv_digest = fin.recv_digest;
+    const u64 te = fin.t_entry, tp = fin.t_posted, tx_ = fin.t_exit, tl = fin.t_loop;
+    mpx_phases& ph = me.phases;
+    ph = mpx_phases{};
+    ph.wall_s = t->wall_s;
+    ph.host_prep_s = t0 - t_call;
+    ph.kernel_s = (te && tx_ >= te) ? (double)(tx_ - te) * 1e-8 : 0;
+    ph.posted_wait_s = (te && tp >= te) ? (double)(tp - te) * 1e-8 : 0;
+    if (t_done > 0 && ph.kernel_s > 0) {
+        ph.launch_to_start_s = (t_done - t0) - ph.kernel_s;
+        ph.done_to_return_s = t_end - t_done;
+    }
+    ph.tail_s = (tl && tx_ >= tl) ? (double)(tx_ - tl) * 1e-8 : 0;
+    if (__atomic_load_n(&me.status->err, __ATOMIC_ACQUIRE)) {
+        me.broken = true;
+        return fail(MPX_ERR_TIMEOUT, "rank %d: a device wait of the fan exchange timed out at iteration %u (%d B to %d peers)",
+                    my_rank, me.status->where - 1, block_len, npeers);
+    }
+    for (int k = 0; k < npeers; ++k) {
+        me.tx_seq[peers[k]] += (u64)iters;
+        me.rx_seq[peers[k]] += (u64)iters;
+    }
+    // the link results, and in check mode every received payload's checksum
+    // against the peer's block, on the host as for the pair loops; on the
+    // rank's own stream (finish_xfer)
+    std::vector<u64> raw(check ? nsum : 0);
+    HIPCK(hipMemcpyAsync(me.fan_host->link, me.fan_tab->link, (size_t)npeers * sizeof(FanLink), hipMemcpyDeviceToHost,
+                         me.stream));
+    if (check && nsum)
+        HIPCK(hipMemcpyAsync(raw.data(), me.csum, nsum * sizeof(u64), hipMemcpyDeviceToHost, me.stream));
+    HIPCK(hipStreamSynchronize(me.stream));
+    const u64 fmix = mix64_host((u64)block_len);
+    int bad = 0;
+    for (int k = 0; k < npeers; ++k) {
+        const FanLink& l = me.fan_host->link[k];
+        u64 dig = 0;
+        int lbad = 0;
+        if (check)
+            for (int i = 0; i < iters; ++i) {
+                const u64 c = raw[(size_t)k * iters + i] ^ fmix;
+                dig += c;
+                if (c != opts->expect_checksum[k]) ++lbad;
+            }
+        bad += lbad;
+        if (!links) continue;
+        links[k].peer = peers[k];
+        links[k].nwg = nwg[k];
+        links[k].recv_done = l.recv_done == ~0ull ? 0 : l.recv_done;
+        links[k].recv_digest = dig;
+        links[k].check_failures = lbad;
+        links[k].device_s = (te && l.t_end >= te) ? (double)(l.t_end - te) * 1e-8 : 0;
+    }
+    if (check) {
+        t->check_iters = nsum;
+        t->check_failures = bad;
+        if (bad)
+            return fail(MPX_ERR_CHECK, "rank %d: %d of %zu received payloads failed the checksum", my_rank, bad, nsum);
+    }
+    return MPX_OK;
 }
 
 namespace {

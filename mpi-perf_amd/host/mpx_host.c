@@ -68,7 +68,8 @@ void mpxh_print_usage(FILE *f)
 		    -S <min:max power-of-two message-size sweep>\n\
 		    -t <device wait timeout ms>\n\
 		    -A <launch each run's kernel before the barrier 0|1 (default 1)>\n\
-		    -L <raw-cap: record every iteration's latency, lat-*.csv (kernel engine, not -x 1)>\n");
+		    -L <raw-cap: record every iteration's latency, lat-*.csv (kernel engine, not -x 1)>\n\
+		    -m <1: every run is one fan exchange, each rank with all others at once (kernel engine)>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -77,7 +78,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -106,7 +107,11 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
         }
         case 't': o->timeout_ms = atoi(optarg); break;
         case 'g': strncpy(o->gpus, optarg, sizeof o->gpus - 1); break;
-        case 'A': o->arm = atoi(optarg); break;
+        case 'A':
+            o->arm = atoi(optarg);
+            o->arm_set = 1;
+            break;
+        case 'm': o->fan = atoi(optarg); break;
         case 'L': {
             char *end = NULL;
             const long v = strtol(optarg, &end, 10);
@@ -121,10 +126,68 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     return MPXH_PARSE_OK;
 }
 
-/* mpi_perf.c:399-403; first the one rule of the new flags that needs two of
-   them: -L traces the kernel engine's blocking loops only */
+size_t mpxh_fan_stride(int buff_len)
+{
+    if (buff_len < 0) return 0;
+    return ((size_t)buff_len + MPXH_FAN_ALIGN - 1) & ~(size_t)(MPXH_FAN_ALIGN - 1);
+}
+
+size_t mpxh_fan_bytes(int world, int buff_len)
+{
+    if (world < 1 || buff_len < 0) return 0;
+    const size_t bytes = (size_t)world * mpxh_fan_stride(buff_len);
+    return bytes > 0x7fffffffull ? 0 : bytes;
+}
+
+int mpxh_fan_peers(int world, int rank, int *peers)
+{
+    int n = 0;
+    for (int q = 0; q < world; ++q)
+        if (q != rank) peers[n++] = q;
+    return n;
+}
+
+/* -m 1 (a fan run) has no pair, no armed call, no recorder, one engine */
+static int validate_fan(const mpxh_options *o, int world, FILE *err)
+{
+    const int top = o->sweep_min > 0 ? o->sweep_max : o->buff_sz;
+    if (o->all_pairs) {
+        fprintf(err, "invalid -m 1 with -a 1: a fan run already has every rank exchange with all others\n");
+        return 1;
+    }
+    if (o->arm_set && o->arm) {
+        fprintf(err, "invalid -m 1 with -A 1: a fan call cannot be armed ahead of the barrier\n");
+        return 1;
+    }
+    if (o->lat_cap >= 0) {
+        fprintf(err, "invalid -m 1 with -L %d: fan calls are never traced by the latency recorder\n", o->lat_cap);
+        return 1;
+    }
+    if (o->engine != 0) {
+        fprintf(err, "invalid -m 1 with -e sdma|rccl: the fan exchange runs on the kernel engine only\n");
+        return 1;
+    }
+    if (o->use_dotnet) {
+        fprintf(err, "invalid -m 1 with -d 1: the .NET launcher lines describe pairs\n");
+        return 1;
+    }
+    if (world < 2) {
+        fprintf(err, "invalid -m 1 with %d rank: a fan run needs at least 2\n", world);
+        return 1;
+    }
+    if (top < 0 || (top > 0 && mpxh_fan_bytes(world, top) == 0)) {
+        fprintf(err, "invalid -m 1 with -b %d: %d blocks of %zu bytes exceed the largest buffer a rank can attach\n", top,
+                world, mpxh_fan_stride(top));
+        return 1;
+    }
+    return 0;
+}
+
+/* mpi_perf.c:399-403; first the rules of the new flags that need two of
+   them: -L traces the kernel engine's blocking loops only, -m 1 (above) */
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
+    if (o->fan && validate_fan(o, world, err)) return 1;
     if (o->lat_cap >= 0 && (o->nonblocking || o->engine != 0)) {
         fprintf(err, "invalid -L %d with %s: per-iteration latencies are recorded by the kernel engine's "
                      "ping-pong and unidir loops only\n",

@@ -46,6 +46,10 @@ typedef struct mpxh_options {
     int lat_cap;                    /* -L  raw_cap: record every iteration's
                                            latency (mpx_lat_*), lat-*.csv;
                                            -1 (default) = off                */
+    int fan;                        /* -m  1 = every run is one fan exchange of
+                                           every rank with all the others
+                                           (mpx_xfer_fan)                     */
+    int arm_set;                    /* -A was given on the command line       */
 } mpxh_options;
 
 /* parse status */
@@ -60,7 +64,7 @@ enum {
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -68,8 +72,21 @@ void mpxh_print_usage(FILE *f);
 int mpxh_engine_from_name(const char *s);
 const char *mpxh_engine_name(int e);
 
-/* validate group_size, mpi_perf.c:399-403, then -L against -x / -e (the
-   recorder traces the kernel engine's blocking loops only).  Returns:
+/* -m 1: blocks of a fan run lie `stride` apart in tx and rx: -b rounded up to
+   4096 (the alignment mpx_alloc gives a buffer) */
+#define MPXH_FAN_ALIGN 4096
+size_t mpxh_fan_stride(int buff_len);
+/* bytes of a fan run's tx (and rx): world blocks; 0 if that exceeds the
+   largest length a rank can attach (2^31 - 1) or an argument is negative */
+size_t mpxh_fan_bytes(int world, int buff_len);
+/* the peers of `rank` in a fan run, in rank order: everyone else.  Returns
+   their number (world - 1). */
+int mpxh_fan_peers(int world, int rank, int *peers);
+
+/* validate -L against -x / -e (the recorder traces the kernel engine's
+   blocking loops only) and -m 1 against -a 1, an explicit -A 1, -L, -e, -d 1
+   and a -b too large for world blocks; then group_size, mpi_perf.c:399-403.
+   Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides
    by zero here (ppn == 0 in bidirectional mode): the caller raises SIGFPE. */
 int mpxh_validate(const mpxh_options *o, int world, FILE *err);

@@ -22,7 +22,9 @@
  * MPX_PROCESSOR_NAMES="a,a,b,b" (indexed by world rank) if set; else, when the
  * ranks span several hosts, the host name, like MPI_Get_processor_name; else
  * (one host) virtual host k = "<host>-<k>" for ranks [k*P, (k+1)*P).  With
- * -a 1 every run is one round of the circle-method all-pairs schedule.
+ * -a 1 every run is one round of the circle-method all-pairs schedule; with
+ * -m 1 every run is one fan exchange: every rank with all the others at once
+ * (mpx_xfer_fan, kernel engine), any world >= 2.
  *
  * Built with -DMPX_WINDOWS_CLI (bin/mpx_perf_win), the front end is the
  * Windows / MS-MPI variant's (/root/reference/windows/mpi-perf.cpp):
@@ -356,11 +358,11 @@ static void *rank_main(void *arg)
                 if (files.gpu_fp) {
                     const double gbps = my_time > 0 ? (double)tm.bytes / my_time / 1e9 : 0.0;
                     static const char *proto[] = {"ll", "bulk", "sdma", "rccl", "copy", "copy_steps", "copy_pipe", "pull",
-                                                 "sdma_pull"};
+                                                 "sdma_pull", "fan"};
                     fprintf(files.gpu_fp, "%s,%s,%d,%s,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%.3f,%s,%d,%llu,%d,%lld,%llu,%llu,%s,%s\n", ts,
                             opt.uuid, r, mpxh_engine_name(opt.engine), xfer_mode(), dev_of[r], peer, dev_of[peer], B,
                             opt.iters, my_time * 1e3, tm.device_s * 1e3, gbps,
-                            (tm.protocol >= 0 && tm.protocol <= 8) ? proto[tm.protocol] : "?", tm.nwg,
+                            (tm.protocol >= 0 && tm.protocol <= 9) ? proto[tm.protocol] : "?", tm.nwg,
                             (unsigned long long)tm.check_iters, tm.check_failures, run_idx,
                             (unsigned long long)tm.recv_done, (unsigned long long)tm.recv_digest,
                             (opt.arm && opt.engine == MPX_ENGINE_KERNEL) ? "armed" : "inline", rccl_build);
@@ -412,6 +414,114 @@ static void *rank_main(void *arg)
     return NULL;
 }
 
+/* ---- -m 1: every run is one fan exchange (mpx_xfer_fan) ------------------- */
+/* Every rank exchanges one -b block with each of the others in one launch.
+   tx and rx hold `world` blocks, mpxh_fan_stride(-b) apart (MPI_Alltoall's
+   layout): block d of tx goes to rank d, block s of rx comes from rank s.
+   The run loop, timing, records and log rotation are rank_main's; there are
+   no groups, so every rank writes its record (VMCount = world, NumOfFlows =
+   world - 1, LocalIP = RemoteIP) and one gpu-*.csv line per link. */
+static uint64_t fansum_of[MPXH_MAX_RANKS][MPXH_MAX_RANKS]; /* [src][dst]: checksum of src's block for dst */
+
+static void share_fan_checksums(int r, const uint64_t *mine)
+{
+    if (procs) {
+        uint64_t row[MPXH_MAX_RANKS] = {0};
+        memcpy(row, mine, (size_t)world * sizeof row[0]);
+        if (mpxb_allgather(boot, row, fansum_of, sizeof row) != 0) boot_failed();
+        return;
+    }
+    barrier(); /* nobody still reads last run's values */
+    memcpy(fansum_of[r], mine, (size_t)world * sizeof mine[0]);
+    barrier();
+}
+
+static void *rank_main_fan(void *arg)
+{
+    const int r = (int)(intptr_t)arg;
+    rank_files files = {NULL, NULL, wtime(), NULL};
+    int peers[MPXH_MAX_RANKS];
+    const int np = mpxh_fan_peers(world, r, peers);
+    for (int si = 0; si < nsizes; ++si) {
+        const int B = sizes[si];
+        const size_t stride = mpxh_fan_stride(B);
+        /* the compat fill: 'a' + src % 26 in every block */
+        if (opt.check != 2)
+            MPX_CHECK(mpx_fill(ctx, dev_of[r], tx_of[r], (size_t)world * stride, MPX_FILL_BYTE, 'a' + r % 26));
+        for (long long run_idx = 0; opt.num_runs == -1 || run_idx < opt.num_runs; run_idx++) {
+            if (opt.check == 2)
+                for (int d = 0; d < world; ++d)
+                    MPX_CHECK(mpx_fill(ctx, dev_of[r], (char *)tx_of[r] + (size_t)d * stride, (size_t)B, MPX_FILL_SPLITMIX,
+                                       mpx_pattern_key(MPX_PATTERN_SEED, (unsigned)r, (unsigned)d, (unsigned)run_idx)));
+            if (files.log_fp == NULL || (wtime() - files.t_last_logtime) > log_refresh_sec) open_logs(r, &files);
+
+            mpx_fan_opts fo;
+            uint64_t expect[MPXH_MAX_RANKS] = {0};
+            memset(&fo, 0, sizeof fo);
+            fo.timeout_ms = (uint32_t)opt.timeout_ms;
+            if (opt.check) {
+                /* the world x world block checksums, read after every fill */
+                uint64_t mine[MPXH_MAX_RANKS] = {0};
+                for (int d = 0; d < world; ++d)
+                    if (d != r)
+                        MPX_CHECK(mpx_checksum(ctx, dev_of[r], (char *)tx_of[r] + (size_t)d * stride, (size_t)B, &mine[d]));
+                share_fan_checksums(r, mine);
+                for (int k = 0; k < np; ++k) expect[k] = fansum_of[peers[k]][r];
+                fo.check = 1;
+                fo.expect_checksum = expect;
+            }
+            start_barrier(); /* MPI_Barrier, mpi_perf.c:499 */
+            const double t_start = wtime();
+            mpx_timing tm;
+            mpx_fan_link links[MPXH_MAX_RANKS];
+            memset(&tm, 0, sizeof tm);
+            MPX_CHECK(mpx_xfer_fan(ctx, r, np, peers, opt.iters, tx_of[r], rx_of[r], B, stride, &fo, &tm, links));
+            const double my_time = wtime() - t_start; /* mpi_perf.c:532-533 */
+
+            if (run_idx > 0) { /* mpi_perf.c:545-555, every rank */
+                char ts[MPXH_MAX_HOST] = {0}, line[1024];
+                mpxh_format_time(ts, sizeof ts, 1);
+                /* (world_size / ppn = world and ppn = world - 1 in the record's terms) */
+                mpxh_format_record(line, sizeof line, ts, opt.uuid, r, world * np, np, ip_of[r], ip_of[r], B, opt.iters,
+                                   my_time, run_idx);
+                if (files.log_fp) fputs(line, files.log_fp);
+                for (int k = 0; files.gpu_fp && k < np; ++k) {
+                    const mpx_fan_link *l = &links[k];
+                    const double gbps = my_time > 0 ? 2.0 * B * opt.iters / my_time / 1e9 : 0.0;
+                    fprintf(files.gpu_fp, "%s,%s,%d,%s,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%.3f,%s,%d,%llu,%d,%lld,%llu,%llu,%s,%s\n", ts,
+                            opt.uuid, r, mpxh_engine_name(opt.engine), MPX_MODE_NONBLOCKING, dev_of[r], l->peer,
+                            dev_of[l->peer], B, opt.iters, my_time * 1e3, l->device_s * 1e3, gbps, "fan", l->nwg,
+                            (unsigned long long)(opt.check ? opt.iters : 0), l->check_failures, run_idx,
+                            (unsigned long long)l->recv_done, (unsigned long long)l->recv_digest, "inline", "");
+                }
+            }
+
+            time_of[r] = my_time;
+            barrier(); /* MPI_Barrier, mpi_perf.c:557 */
+            const double t_end = wtime();
+            double mn = my_time, mx = my_time, sum = my_time; /* Allreduce MIN/MAX/SUM, mpi_perf.c:560-562 */
+            if (procs) {
+                if (mpxb_allreduce_f64(boot, my_time, &mn, &mx, &sum) != 0) boot_failed();
+            } else if (r == 0) {
+                sum = 0;
+                for (int q = 0; q < world; ++q) {
+                    if (time_of[q] < mn) mn = time_of[q];
+                    if (time_of[q] > mx) mx = time_of[q];
+                    sum += time_of[q];
+                }
+            }
+            if (r == 0 && (run_idx % 1000 == 0)) { /* mpi_perf.c:564-568 */
+                char line[256];
+                mpxh_format_summary(line, sizeof line, run_idx, t_end - t_start, mn, mx, sum, world);
+                fputs(line, stderr);
+            }
+        }
+    }
+    if (files.log_fp) fclose(files.log_fp);
+    if (files.gpu_fp) fclose(files.gpu_fp);
+    return NULL;
+}
+
 /* ---- processes mode: the reference's once-per-job collectives ------------ */
 
 /* MPI_Bcast of the options (with rank 0's UUID) and of the group-1 host
@@ -450,11 +560,11 @@ static void share_node_info(const char *node, const char *ip, int dev)
     }
 }
 
-/* Peers this rank transfers with: its fixed peer, or everyone (-a 1). */
+/* Peers this rank transfers with: its fixed peer, or everyone (-a 1, -m 1). */
 static int needs_peer(int q)
 {
     if (q == me) return 0;
-    return opt.all_pairs || peer_of[me] == q;
+    return opt.all_pairs || opt.fan || peer_of[me] == q;
 }
 
 /* The kernel and SDMA engines write into a peer's HBM: both ranks of every
@@ -667,7 +777,7 @@ int main(int argc, char **argv)
         mpxh_pairing(world, group_of, grank_of, gsize_of, peer_of);
     free(group1);
 
-    if (win_cli && !opt.all_pairs) {
+    if (win_cli && !opt.all_pairs && !opt.fan) {
         /* every rank prints its INFO line to stdout right after the pairing
            (windows/mpi-perf.cpp:303-306); a rank without a peer dereferences
            the NULL peer_node_info there */
@@ -683,7 +793,7 @@ int main(int argc, char **argv)
         fflush(stdout);
     }
 
-    if (!opt.all_pairs) {
+    if (!opt.all_pairs && !opt.fan) { /* (a fan run uses no pairing: any world >= 2, odd included) */
         for (int r = 0; r < world; ++r) {
             if (peer_of[r] < 0 && (!procs || r == me)) { /* get_ipaddress(NULL peer), mpi_perf.c:180-184 */
                 fprintf(stderr, "getaddrinfo error: rank %d (%s) has no peer in the other group\n", r, name_of[r]);
@@ -714,7 +824,9 @@ int main(int argc, char **argv)
             snprintf(ip_of[r], sizeof ip_of[r], "%s", node_ip); /* the host's IPv4, mpi_perf.c:236-237 */
         }
     }
-    if (!opt.all_pairs && !win_cli) {
+    if (opt.fan) {
+        if (is_root()) fprintf(stderr, "FAN: each of %d ranks exchanges with its %d peers in one launch\n", world, world - 1);
+    } else if (!opt.all_pairs && !win_cli) {
         for (int r = 0; r < world; ++r) {
             if (procs && r != me) continue; /* every rank prints its own line, mpi_perf.c:460-461 */
             char line[1024];
@@ -742,6 +854,8 @@ int main(int argc, char **argv)
     int maxb = 1;
     for (int i = 0; i < nsizes; ++i)
         if (sizes[i] > maxb) maxb = sizes[i];
+    /* -m 1: tx and rx hold one block per rank (validated: within an attachable length) */
+    if (opt.fan) maxb = (int)mpxh_fan_bytes(world, maxb);
 
     if (procs && !opt.use_dotnet) {
         MPX_CHECK(mpx_device_count(&ndev));
@@ -772,7 +886,7 @@ int main(int argc, char **argv)
     if (procs) {
         open_start_barrier();
         barrier();
-        rank_main((void *)(intptr_t)me);
+        (opt.fan ? rank_main_fan : rank_main)((void *)(intptr_t)me);
         barrier(); /* MPI_Barrier, mpi_perf.c:579: no peer still maps our buffers */
         if (ctx) MPX_CHECK(mpx_finalize(ctx)); /* frees tx/rx too */
         /* the pooled rank streams go before exit, as in threads mode below.
@@ -792,7 +906,7 @@ int main(int argc, char **argv)
     pthread_barrier_init(&bar, NULL, (unsigned)world);
     open_start_barrier();
     pthread_t th[MPXH_MAX_RANKS];
-    for (int r = 0; r < world; ++r) pthread_create(&th[r], NULL, rank_main, (void *)(intptr_t)r);
+    for (int r = 0; r < world; ++r) pthread_create(&th[r], NULL, opt.fan ? rank_main_fan : rank_main, (void *)(intptr_t)r);
     for (int r = 0; r < world; ++r) pthread_join(th[r], NULL);
     pthread_barrier_destroy(&bar);
     mpxb_spin_close(start_bar, 0);

@@ -36,7 +36,8 @@ PATTERN_SEED = 0x6D70695F70657266
 MAX_RANKS = 64
 RANK_DESC_BYTES = 512
 RCCL_ID_BYTES = 128
-PROTOCOLS = {0: "ll", 1: "bulk", 2: "sdma", 3: "rccl", 4: "copy", 5: "copy_steps", 6: "copy_pipe", 7: "pull", 8: "sdma_pull"}
+PROTOCOLS = {0: "ll", 1: "bulk", 2: "sdma", 3: "rccl", 4: "copy", 5: "copy_steps", 6: "copy_pipe", 7: "pull", 8: "sdma_pull",
+             9: "fan"}
 
 
 class Timing(C.Structure):
@@ -68,6 +69,33 @@ class XferOpts(C.Structure):
         ("timeout_ms", C.c_uint32),
         ("nwg", C.c_int32),
     ]
+
+
+class FanOpts(C.Structure):
+    """mpx_fan_opts"""
+    _fields_ = [
+        ("check", C.c_int32),
+        ("flags", C.c_int32),
+        ("timeout_ms", C.c_uint32),
+        ("nwg", C.c_int32),
+        ("expect_checksum", C.POINTER(C.c_uint64)),
+    ]
+
+
+class FanLink(C.Structure):
+    """mpx_fan_link: one link's results of a fan call"""
+    _fields_ = [
+        ("peer", C.c_int32),
+        ("nwg", C.c_int32),
+        ("recv_done", C.c_uint64),
+        ("recv_digest", C.c_uint64),
+        ("check_failures", C.c_int32),
+        ("pad", C.c_int32),
+        ("device_s", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 class Phases(C.Structure):
@@ -163,6 +191,9 @@ _SIGS = {
                            C.c_int, C.POINTER(C.c_double)]),
     "mpx_xfer_ex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                               C.c_int, C.POINTER(XferOpts), C.POINTER(Timing)]),
+    "mpx_xfer_fan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_int, C.c_size_t, C.POINTER(FanOpts), C.POINTER(Timing), C.POINTER(FanLink)]),
+    "mpx_fan_width": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mpx_xfer_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(XferOpts)]),
     "mpx_xfer_arm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -227,6 +258,11 @@ def link_info(dev_a: int, dev_b: int) -> dict:
     t, h = C.c_int(0), C.c_int(0)
     check(lib().mpx_link_info(dev_a, dev_b, C.byref(t), C.byref(h)), "mpx_link_info")
     return {"type": LINK_TYPES.get(t.value, t.value), "hops": h.value}
+
+
+def fan_width(nranks: int, block_len: int, same_device: bool = True, nwg: int = 0) -> int:
+    """mpx_fan_width: the width mpx_xfer_fan gives a link (-1: refused)"""
+    return lib().mpx_fan_width(nranks, block_len, 1 if same_device else 0, nwg)
 
 
 def shutdown() -> None:
@@ -338,6 +374,31 @@ class Context:
                                     C.c_void_p(rx.ptr), length, C.byref(o), C.byref(t))
         check(st, "mpx_xfer_ex")
         return t
+
+    def fan(self, my_rank: int, peers, iters: int, tx: Buffer, rx: Buffer, block_len: int, stride: int,
+            check_payload: bool = False, expect=None, timeout_ms: int = 0, nwg: int = 0, stream: bool = False):
+        """mpx_xfer_fan: my_rank exchanges block_len bytes with every rank of
+        `peers` in one launch (block j of tx / rx at j * stride).  expect:
+        check mode, the checksum of each peer's block for my_rank, in the
+        order of `peers`.  Returns (Timing, [link dicts]); a failing call
+        raises MpxError carrying .timing and .links as far as they were
+        filled."""
+        peers = list(peers)
+        n = len(peers)
+        arr = (C.c_int * max(n, 1))(*peers)
+        exp = (C.c_uint64 * max(n, 1))(*(list(expect) if expect is not None else [0] * n))
+        o = FanOpts(check=1 if check_payload else 0, flags=XFER_STREAM if stream else 0, timeout_ms=timeout_ms,
+                    nwg=nwg, expect_checksum=C.cast(exp, C.POINTER(C.c_uint64)))
+        t = Timing()
+        links = (FanLink * max(n, 1))()
+        st = self.L.mpx_xfer_fan(self.h, my_rank, n, arr, iters, C.c_void_p(tx.ptr), C.c_void_p(rx.ptr), block_len,
+                                 stride, C.byref(o), C.byref(t), links)
+        out = [links[k].as_dict() for k in range(n)]
+        if st != OK:
+            e = MpxError(st, "mpx_xfer_fan")
+            e.timing, e.links = t, out
+            raise e
+        return t, out
 
     def arm(self, mode: int, group: int, my_rank: int, peer_rank: int, iters: int, tx: Buffer, rx: Buffer,
             length: int, check_payload: bool = False, expect: int = 0, expect_ack: int = 0, timeout_ms: int = 0,
