@@ -6,6 +6,12 @@ checked full-mesh fan exchange: one link to the rank next door, two over
 imported ranks.  tx is written from host bytes, seeded per (src, dst), so the
 other process's blocks are known here without asking it; rx is 0xEE before
 the call and compared whole after it.  Results go to <dir>/result_<p>.json.
+
+An optional third argument jump=<next_push> (tests/test_gpu_fan_wrap.py): right
+after attach and import, this process advances its own side of every link of
+its ranks, the links to imported ranks included, so that the link's next push
+is that number (mpx_test_advance_link: each process its own side); the link
+counters before and after the call go into the result.
 """
 import json
 import os
@@ -41,6 +47,7 @@ def wait_for(path):
 
 def main():
     d, p = sys.argv[1], int(sys.argv[2])
+    jump = int(sys.argv[3].split("=", 1)[1]) if len(sys.argv) > 3 and sys.argv[3].startswith("jump=") else 0
     mine = [2 * p, 2 * p + 1]
     theirs = [r for r in range(WORLD) if r not in mine]
     c = mpx.Context(WORLD, "kernel")
@@ -62,6 +69,11 @@ def main():
     for r in theirs:
         wait_for(os.path.join(d, f"desc_{r}.bin"))
         c.import_rank(r, open(os.path.join(d, f"desc_{r}.bin"), "rb").read())
+    if jump:
+        for r in mine:
+            for q in range(WORLD):
+                if q != r:
+                    c.test_advance_link(r, q, jump - 1, 0, 0)
     results, errs = [], []
 
     def side(r):
@@ -69,6 +81,7 @@ def main():
         if r % 2:
             peers.reverse()
         sums = [O.checksum(block(q, r)) for q in peers]
+        before = {q: c.link_counters(r, q) for q in peers}
         try:
             t, links = c.fan(r, peers, ITERS, bufs[r][0], bufs[r][1], N, STRIDE, check_payload=True, expect=sums,
                              timeout_ms=20000)
@@ -80,6 +93,7 @@ def main():
             want[q * STRIDE:q * STRIDE + N] = block(q, r)
         results.append(dict(rank=r, iters=ITERS, check_iters=t.check_iters, check_failures=t.check_failures,
                             recv_done=t.recv_done, protocol=t.protocol, links=links,
+                            before=[before[q] for q in peers], after=[c.link_counters(r, q) for q in peers],
                             digest_ok=t.recv_digest == sum(ITERS * s for s in sums) & M64,
                             rx_ok=c.read(bufs[r][1], CAP) == bytes(want), tx_ok=c.read(bufs[r][0], CAP) == host[r]))
 
