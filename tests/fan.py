@@ -78,18 +78,24 @@ def links_of(peersets: dict) -> list:
 
 
 class Fan:
-    def __init__(self, nranks: int, cap: int, engine="kernel"):
+    """ranks: the ranks attached, of the context's nranks (default: all of
+    them); caps: rank -> attached length where it is not cap"""
+
+    def __init__(self, nranks: int, cap: int, engine="kernel", ranks=None, caps=None):
         self.n = nranks
+        self.ranks = list(range(nranks)) if ranks is None else list(ranks)
         self.cap = cap
+        self.caps = {r: (caps or {}).get(r, cap) for r in self.ranks}
         self.c = mpx.Context(nranks, engine)
-        self.bufs = []
-        self.host = [b""] * nranks
+        self.bufs = {}
+        self.host = [b""] * nranks      # by rank number; a rank not attached holds nothing
         self.block_len = self.stride = 0
         self.seed = 0
-        for r in range(nranks):
-            tx, rx = self.c.alloc(0, cap), self.c.alloc(0, cap)
-            self.c.attach(r, 0, tx, rx, cap)
-            self.bufs.append((tx, rx))
+        for r in self.ranks:
+            n = self.caps[r]
+            tx, rx = self.c.alloc(0, n), self.c.alloc(0, n)
+            self.c.attach(r, 0, tx, rx, n)
+            self.bufs[r] = (tx, rx)
 
     def close(self):
         self.c.close()
@@ -98,8 +104,8 @@ class Fan:
         """every rank's tx, written from the host for this block layout"""
         assert self.n * stride <= self.cap and block_len <= stride
         self.block_len, self.stride = block_len, stride
-        for r in range(self.n):
-            self.host[r] = tx_image(self.cap, self.n, r, block_len, stride, self.seed)
+        for r in self.ranks:     # (a rank attached shorter holds the front of the image)
+            self.host[r] = tx_image(self.cap, self.n, r, block_len, stride, self.seed)[:self.caps[r]]
             payload.write(self.c, self.bufs[r][0], self.host[r])
 
     def set_tx_seed(self, k: int) -> None:
@@ -111,23 +117,23 @@ class Fan:
         self.seed = k
         self.layout(self.block_len, self.stride)
         if self.block_len >= 16:
-            for r in range(self.n):
-                for d in range(self.n):
+            for r in self.ranks:
+                for d in self.ranks:
                     assert self.block(r, d) != old[r][d * self.stride:d * self.stride + self.block_len], (r, d)
 
     def fill_tx(self, r: int, seed: int) -> None:
         """rank r's own tx = flat_image(cap, r, seed), written by the device
         (mpx_fill, the utility stream): safe while peers are inside a call.
         self.host is the caller's to update once no thread reads it."""
-        self.c.fill(self.bufs[r][0], self.cap, mpx.FILL_SPLITMIX, flat_key(r, seed))
+        self.c.fill(self.bufs[r][0], self.caps[r], mpx.FILL_SPLITMIX, flat_key(r, seed))
 
     def block(self, src: int, dst: int) -> bytes:
         """what src sends dst"""
         return self.host[src][dst * self.stride:dst * self.stride + self.block_len]
 
     def prefill(self) -> None:
-        for r in range(self.n):
-            self.c.fill(self.bufs[r][1], self.cap, mpx.FILL_BYTE, payload.GUARD_BYTE)
+        for r in self.ranks:
+            self.c.fill(self.bufs[r][1], self.caps[r], mpx.FILL_BYTE, payload.GUARD_BYTE)
 
     def run(self, peersets: dict, iters: int, check=True, timeout_ms=5000, prefill=True, late=None, **kw):
         """peersets: rank -> its peers, in the order it lists them; every
@@ -144,14 +150,14 @@ class Fan:
             exp = [O.checksum(self.block(p, r)) for p in peersets[r]]
             if late and r in late:
                 time.sleep(late[r])
-                self.rx_before[r] = self.c.read(self.bufs[r][1], self.cap)
+                self.rx_before[r] = self.c.read(self.bufs[r][1], self.caps[r])
             try:
                 out[r] = self.c.fan(r, peersets[r], iters, self.bufs[r][0], self.bufs[r][1], self.block_len, self.stride,
                                     check_payload=check, expect=exp, timeout_ms=timeout_ms, **kw)
             except mpx.MpxError as e:
                 errs[r] = e
             if late is not None:
-                self.rx_at_return[r] = self.c.read(self.bufs[r][1], self.cap)
+                self.rx_at_return[r] = self.c.read(self.bufs[r][1], self.caps[r])
 
         th = [threading.Thread(target=side, args=(r,)) for r in peersets]
         for t in th:
@@ -170,8 +176,8 @@ class Fan:
         def call():
             out, errs = self.run(peersets, iters, check=check, late=late, **kw)
             assert not errs, (what, errs)
-            blank = bytes([payload.GUARD_BYTE]) * self.cap
             for r in late:
+                blank = bytes([payload.GUARD_BYTE]) * self.caps[r]
                 payload.compare(self.rx_before[r], blank, 0, f"{what}: rx of late rank {r} before its call")
             for r, peers in peersets.items():
                 payload.compare(self.rx_at_return[r], self.expected_rx(r, peers, iters > 0), 0,
@@ -184,7 +190,7 @@ class Fan:
         return self.counted(peersets, iters, call)
 
     def expected_rx(self, r: int, peers, moved=True) -> bytes:
-        want = bytearray([payload.GUARD_BYTE]) * self.cap
+        want = bytearray([payload.GUARD_BYTE]) * self.caps[r]
         if moved:
             for p in peers:
                 want[p * self.stride:p * self.stride + self.block_len] = self.block(p, r)
@@ -193,11 +199,11 @@ class Fan:
     def verify_bytes(self, peersets: dict, what, moved=True) -> None:
         """rx whole (the peers' blocks, 0xEE everywhere else: the gaps, the
         rank's own block, the blocks of ranks outside the set) and tx whole"""
-        for r in range(self.n):
+        for r in self.ranks:
             peers = peersets.get(r, [])
-            payload.compare(self.c.read(self.bufs[r][1], self.cap), self.expected_rx(r, peers, moved), 0,
+            payload.compare(self.c.read(self.bufs[r][1], self.caps[r]), self.expected_rx(r, peers, moved), 0,
                             f"{what}: rx of rank {r}")
-            payload.compare(self.c.read(self.bufs[r][0], self.cap), self.host[r], 0, f"{what}: tx of rank {r}")
+            payload.compare(self.c.read(self.bufs[r][0], self.caps[r]), self.host[r], 0, f"{what}: tx of rank {r}")
 
     def verify(self, peersets: dict, out: dict, iters: int, check: bool, what, widths=None) -> None:
         """the bytes, and everything the call reports: per link and in total"""
@@ -258,7 +264,7 @@ class Fan:
         seen from both sides: iters pushes each way and one call on a link of
         the peer graph (no call number for iters = 0), nothing on any other
         link; one token for every rank that called"""
-        pairs = [(r, p) for r in range(self.n) for p in range(self.n) if p != r]
+        pairs = [(r, p) for r in self.ranks for p in range(self.n) if p != r]
         before = {k: self.counters(*k) for k in pairs}
         out = call()
         for (r, p), b in before.items():

@@ -27,15 +27,18 @@ CREDIT_RING = 2 * CREDIT_CAP      # MPX_CHECK_RING_BYTES: two slots of the attac
 class HostPairs(Pairs):
     """one loopback pair (the kernel engine unless told otherwise) with seeded
     tx, whose expected bytes and checksums all come from the host: host[r] =
-    what rank r's tx holds"""
+    what rank r's tx holds.  ranks, nranks, caps: tests/pairs.py (ranks =
+    [group 1's ranks..., their peers...]; the default is the pair (0, 1) of a
+    two-rank context, rank 0 group 1); npairs > 1: that many pairs"""
 
-    def __init__(self, cap, engine="kernel"):
-        super().__init__(engine, 1, cap, fill="seeded")
-        self.host = [O.fill(cap, mpx.FILL_SPLITMIX, mpx.pattern_key(mpx.PATTERN_SEED, r, 0, 0)) for r in (0, 1)]
+    def __init__(self, cap, engine="kernel", ranks=None, nranks=None, caps=None, npairs=1):
+        super().__init__(engine, npairs, cap, fill="seeded", ranks=ranks, nranks=nranks, caps=caps)
+        self.host = {r: O.fill(self.caps[r], mpx.FILL_SPLITMIX, mpx.pattern_key(mpx.PATTERN_SEED, r, 0, 0))
+                     for r in self.ranks}
 
     def set_tx(self, data: bytes):
-        """both ranks' tx[0 : len(data)) = data (between calls)"""
-        for r in (0, 1):
+        """every rank's tx[0 : len(data)) = data (between calls)"""
+        for r in self.ranks:
             payload.write(self.c, self.bufs[r][0], data)
             self.host[r] = data + self.host[r][len(data):]
 
@@ -45,8 +48,8 @@ class HostPairs(Pairs):
         return O.checksum(h[:n]), O.checksum(h[:1])
 
     def advance(self, seq_by=0, calls_by=0, token_by=0):
-        """both ranks of the link jump forward alike (between calls)"""
-        for r in (0, 1):
+        """both ranks of every link jump forward alike (between calls)"""
+        for r in self.ranks:
             self.c.test_advance_link(r, self.peer(r), seq_by, calls_by, token_by)
 
     def counters(self, r):
@@ -54,41 +57,43 @@ class HostPairs(Pairs):
         return self.c.link_counters(r, self.peer(r))
 
 
-def received(mode, r, n):
-    """bytes rank r receives per message: B, or unidir's 1-byte ack (rank 0 =
-    group 1, mpi_perf.c:137,142)"""
-    return 1 if (mode == UNIDIR and r == 0) else n
+def received(mode, r, n, group1=(0,)):
+    """bytes rank r receives per message: B, or unidir's 1-byte ack (group 1,
+    mpi_perf.c:137,142; rank 0 in the default pair)"""
+    return 1 if (mode == UNIDIR and r in group1) else n
 
 
 def run_checked(P, mode, n, iters, what, **kw):
     """one checked call on a 0xEE-prefilled rx, then everything a caller can
     see: no error, every payload checked, the reference's receive count, the
-    host-computed digest, rx byte for byte with its guard, tx untouched"""
-    for r in (0, 1):      # (max: the 1-byte ack of a 0-byte unidir message has its guard too)
+    host-computed digest, rx byte for byte with its guard, tx untouched
+    (check=False: an unchecked call, which checks and digests nothing)"""
+    chk = kw.get("check", True)
+    for r in P.ranks:      # (max: the 1-byte ack of a 0-byte unidir message has its guard too)
         P.c.fill(P.bufs[r][1], max(n, 1) + GUARD, mpx.FILL_BYTE, payload.GUARD_BYTE)
     out, errs = P.run(mode, n, iters, **kw)
     assert not errs, (what, errs)
     done = O.lib().oracle_nb_waited(iters) if mode == NONBLOCKING else iters
-    for r in (0, 1):
+    for r in P.ranks:
         t = out[r]
-        expected = P.host[P.peer(r)][:received(mode, r, n)]
-        assert t.check_failures == 0 and t.check_iters == iters, (what, r, t.check_failures, t.check_iters)
+        expected = P.host[P.peer(r)][:received(mode, r, n, P.group1)]
+        assert t.check_failures == 0 and t.check_iters == (iters if chk else 0), (what, r, t.check_iters)
         assert t.recv_done == done, (what, r, t.recv_done)
-        assert t.recv_digest == (done * O.checksum(expected)) & M64, (what, r)
+        assert not chk or t.recv_digest == (done * O.checksum(expected)) & M64, (what, r)
         assert_region(P.c, P.bufs[r][1], 0, expected, what=f"{what}: rx of rank {r}")
         # (the whole of tx, not only the n bytes sent: a push that landed in it lands anywhere)
-        payload.compare(P.c.read(P.bufs[r][0], P.cap), P.host[r], 0, f"{what}: tx of rank {r} after the call")
+        payload.compare(P.c.read(P.bufs[r][0], P.caps[r]), P.host[r], 0, f"{what}: tx of rank {r} after the call")
     return out
 
 
 def jump(P, next_push):
     """both ranks of the link: the next push is number `next_push`"""
-    c = [P.counters(r) for r in (0, 1)]
+    c = [P.counters(r) for r in P.ranks]
     last = c[0]["tx_seq"]
     assert all(x["tx_seq"] == last and x["rx_seq"] == last for x in c), c
     assert next_push - 1 > last
     P.advance(seq_by=next_push - 1 - last)
-    for r in (0, 1):
+    for r in P.ranks:
         assert P.counters(r)["tx_seq"] == P.counters(r)["rx_seq"] == next_push - 1
 
 
@@ -96,9 +101,9 @@ def counted(P, iters, call, what):
     """call(), and what it must have added to both ranks' counters: iters
     pushes each way, one call on the link (none for iters = 0), one token on
     the kernel engine"""
-    before = [P.counters(r) for r in (0, 1)]
+    before = {r: P.counters(r) for r in P.ranks}
     out = call()
-    for r in (0, 1):
+    for r in P.ranks:
         b, a = before[r], P.counters(r)
         assert a["tx_seq"] == b["tx_seq"] + iters and a["rx_seq"] == b["rx_seq"] + iters, (what, r, b, a)
         assert a["calls"] == b["calls"] + (1 if iters > 0 else 0), (what, r, b, a)

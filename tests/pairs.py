@@ -9,6 +9,12 @@ like one MPI rank each.
 pairs: the kernel, mailbox protocol and sequence bookkeeping of the cross-GPU
 path, with the peer's HBM being local HBM); `cross_gpu_devs()` puts every
 rank on a GPU of its own, so each pair moves its bytes over xGMI.
+
+`ranks` gives the 2 * npairs ranks numbers of their own in a context of
+`nranks` ranks (default: the largest number + 1), of which only these are
+attached: ranks[k] is group 1 and paired with ranks[np + k].  `caps` (rank ->
+bytes) attaches single ranks with another length than `cap`.  The defaults are
+the layout above.
 """
 from __future__ import annotations
 
@@ -35,31 +41,41 @@ def cross_gpu_devs(nranks: int) -> list[int] | None:
 
 
 class Pairs:
-    def __init__(self, engine, npairs, cap, fill="compat", devs=None):
-        self.c = mpx.Context(2 * npairs, engine)
+    def __init__(self, engine, npairs, cap, fill="compat", devs=None, ranks=None, nranks=None, caps=None):
         self.np = npairs
+        self.ranks = list(range(2 * npairs)) if ranks is None else list(ranks)
+        assert len(self.ranks) == 2 * npairs == len(set(self.ranks)), self.ranks
+        self.group1 = self.ranks[:npairs]
+        self._peer = {}
+        for k in range(npairs):
+            a, b = self.ranks[k], self.ranks[npairs + k]
+            self._peer[a], self._peer[b] = b, a
+        self.nranks = max(self.ranks) + 1 if nranks is None else nranks
+        self.c = mpx.Context(self.nranks, engine)
         self.cap = cap
-        self.devs = list(devs) if devs is not None else [0] * (2 * npairs)
-        assert len(self.devs) == 2 * npairs
-        self.bufs = []
-        for r in range(2 * npairs):
-            d = self.devs[r]
-            tx, rx = self.c.alloc(d, cap), self.c.alloc(d, cap)
+        self.caps = {r: (caps or {}).get(r, cap) for r in self.ranks}
+        devs = list(devs) if devs is not None else [0] * (2 * npairs)
+        assert len(devs) == 2 * npairs
+        self.devs = devs
+        self.bufs = {}      # rank -> (tx, rx)
+        for r, d in zip(self.ranks, devs):
+            n = self.caps[r]
+            tx, rx = self.c.alloc(d, n), self.c.alloc(d, n)
             if fill == "compat":   # mpi_perf.c:244-251: group 0 'a', group 1 'b'
-                self.c.fill(tx, cap, mpx.FILL_BYTE, ord("b") if r < npairs else ord("a"))
+                self.c.fill(tx, n, mpx.FILL_BYTE, ord("b") if r in self.group1 else ord("a"))
             else:
-                self.c.fill(tx, cap, mpx.FILL_SPLITMIX, mpx.pattern_key(mpx.PATTERN_SEED, r, 0, 0))
-            self.c.fill(rx, cap, mpx.FILL_BYTE, 0)
-            self.c.attach(r, d, tx, rx, cap)
-            self.bufs.append((tx, rx))
+                self.c.fill(tx, n, mpx.FILL_SPLITMIX, mpx.pattern_key(mpx.PATTERN_SEED, r, 0, 0))
+            self.c.fill(rx, n, mpx.FILL_BYTE, 0)
+            self.c.attach(r, d, tx, rx, n)
+            self.bufs[r] = (tx, rx)
         if self.c.engine == mpx.ENGINE_RCCL:
             self.c.rccl_init_all()
 
     def peer(self, r):
-        return r + self.np if r < self.np else r - self.np
+        return self._peer[r]
 
     def group(self, r):
-        return 1 if r < self.np else 0
+        return 1 if r in self.group1 else 0
 
     def expect(self, r, n):
         tx = self.bufs[self.peer(r)][0]
@@ -70,7 +86,7 @@ class Pairs:
         """every rank's side on a thread of its own; armed: each side arms
         its call (mpx_xfer_arm), all sides meet at a barrier (the hosts'
         mpi_perf.c:499), then start it"""
-        ranks = list(range(2 * self.np)) if ranks is None else ranks
+        ranks = list(self.ranks) if ranks is None else ranks
         exp = {r: self.expect(r, n) for r in ranks}
         out, errs = {}, {}
         bar = threading.Barrier(len(ranks))

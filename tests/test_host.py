@@ -65,7 +65,8 @@ def test_group_and_pairing_match_reference(H, name):
     assert pairing_from_groups(groups) == (list(gr), list(pe))
 
 
-@pytest.mark.parametrize("name", [c["name"] for c in G["cases"] if len(c["info"]) == c["np"] and c["info"]][:12])
+@pytest.mark.parametrize("name", [c["name"] for c in G["cases"] if len(c["info"]) == c["np"] and c["info"]][:12]
+                         + [c["name"] for c in G["cases"] if c["ppn"] == 10])
 def test_info_line_format(H, name):
     c = CASES[name]
     for d in c["info"]:
@@ -136,7 +137,10 @@ def test_every_round_is_a_reference_run_with_ppn_half(H, n, mode):
         assert sorted(sigma[w] for w in writers) == sorted(pairs[2 * k] for k in range(n // 2))
 
 
-@pytest.mark.parametrize("name", [c["name"] for c in G["cases"] if c["records"]][:20])
+P10 = [c["name"] for c in G["cases"] if c["ppn"] == 10]      # world 20: scripts/run-hbv3.sh's shape
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in G["cases"] if c["records"]][:20] + P10)
 def test_record_format_matches_reference(H, name):
     c = CASES[name]
     ppn = int(c["args"][c["args"].index("-p") + 1])

@@ -34,8 +34,35 @@ def _arg(case, flag, default):
 def test_golden_has_every_mode_and_ppn():
     names = set(CASES)
     for m in MODE_OF:
-        for p in (1, 2, 4):
-            assert any(n.startswith(f"{m}_p{p}_") for n in names)
+        for p in (1, 2, 4, 10):
+            assert any(n.startswith(f"{m}_p{p}_") and CASES[n]["ppn"] == p and CASES[n]["np"] == 2 * p
+                       for n in names), (m, p)
+
+
+def test_hbv3_ten_flow_contract():
+    """scripts/run-hbv3.sh's shape (-u 1 -p 10 -b 456131 -i 10 on two hosts,
+    here with -r 3), as the compiled reference ran it: world 20, ranks 0-9
+    are group 1 and rank k is paired with 10 + k; every record says VMCount 2
+    and NumOfFlows 10; every rank completed 30 receives (10 per run: payloads
+    on group 0, 1-byte acks on group 1)."""
+    c = CASES["unidir_p10_b456131_i10"]
+    assert (c["np"], c["ppn"], c["returncode"]) == (20, 10, 0)
+    assert [d["rank"] for d in c["info"]] == list(range(20))
+    for d in c["info"]:
+        k = d["rank"]
+        assert d["world"] == 20 and d["group_size"] == 10 and d["group_rank"] == k % 10, d
+        assert d["group"] == (1 if k < 10 else 0) and d["peer"] == (k + 10 if k < 10 else k - 10), d
+    assert c["n_records"] == 10 * 2 and sorted(f["rank"] for f in c["files"]) == list(range(10))
+    assert c["records"][0]["line_masked"] == "T,U,0,2,127.0.0.1,127.0.0.1,10,456131,10,X,1"
+    for rec in c["records"]:
+        assert (rec["vmcount"], rec["flows"], rec["buffer_size"], rec["num_buffers"]) == (2, 10, 456131, 10), rec
+    assert sorted(c["shim"], key=int) == [str(r) for r in range(20)]
+    for r in range(20):
+        s = c["shim"][str(r)]
+        assert s["recv_done"] == 30 and s["recv_bytes"] == 30 * (1 if r < 10 else 456131), (r, s)
+    one = O.checksum(b"b" * 456131)     # group 1 sends 'b', group 0 acks with 'a' (mpi_perf.c:244-251)
+    assert all(c["shim"][str(r)]["recv_digest"] == (30 * one) & 0xFFFFFFFFFFFFFFFF for r in range(10, 20))
+    assert all(c["shim"][str(r)]["recv_digest"] == (30 * O.checksum(b"a")) & 0xFFFFFFFFFFFFFFFF for r in range(10))
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in G["cases"] if c["info"]])
@@ -60,7 +87,7 @@ def test_strnicmp_prefix_semantics():
     assert O.in_group1("runsc", ["vm"]) == 0
 
 
-LOOP_CASES = [c["name"] for c in G["cases"] if re.match(r"(pingpong|nonblocking|unidir)_p\d_b\d+_i\d+$", c["name"])]
+LOOP_CASES = [c["name"] for c in G["cases"] if re.match(r"(pingpong|nonblocking|unidir)_p\d+_b\d+_i\d+$", c["name"])]
 LOOP_CASES += ["defaults_unidir", "zero_bytes_pingpong", "zero_bytes_unidir", "zero_bytes_nonblocking",
                "group_upper_prefix_line"]
 
