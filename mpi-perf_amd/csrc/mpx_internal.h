@@ -1,5 +1,7 @@
-// mpx_internal.h — types shared by the libmpx runtime (mpx_runtime.hip) and
-// its device code (mpx_kernels.hip).  Not part of the C-ABI.
+// mpx_internal.h — types shared by the libmpx host side (mpx_runtime.hip,
+// mpx_engine_kernel.hip, mpx_engine_stream.hip; their own shared declarations
+// are in mpx_runtime.h) and its device code (mpx_kernels.hip).  Not part of
+// the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -227,7 +229,7 @@ __host__ __device__ inline unsigned ll_tag(u64 seq) {
 
 // Workgroups of a bulk push of `len` bytes.  Both sides of a link evaluate
 // this on the same inputs, so the receiver knows how many flags to expect.
-constexpr long long kMinPushChunk = 1024;   // bytes per pushing workgroup, at least (run_kernel)
+constexpr long long kMinPushChunk = 1024;   // bytes per pushing workgroup, at least (link_nwg)
 inline int bulk_nwg(long long len, bool same_device) {
     // ~32 KiB per workgroup across xGMI (enough 16-B stores in flight to
     // cover the link's bandwidth-delay product), 16 KiB within one GPU.
@@ -240,6 +242,20 @@ inline int bulk_nwg(long long len, bool same_device) {
     if (n < 1) n = 1;
     if (n > cap) n = cap;
     return (int)n;
+}
+// The width of a link, pair or fan: the call's option, else the environment's
+// value (MPX_PUSH_WG, MPX_FAN_WG), else the default rule's (bulk_nwg,
+// fan_default_nwg); 0 if that exceeds kMaxPushWG (invalid).  A width chosen
+// for large pushes is not applied to small ones: at least kMinPushChunk bytes
+// per workgroup, and at least one workgroup (the size rule's chunks are
+// 16-32 KiB, so it never narrows them).  Both sides of a link compute it from
+// the same inputs, so they agree.
+inline int link_nwg(int opt, int env, int dflt, long long len) {
+    const int w = opt > 0 ? opt : env > 0 ? env : dflt;
+    if (w > kMaxPushWG) return 0;
+    const long long most = (len + kMinPushChunk - 1) / kMinPushChunk;
+    const long long n = w < most ? w : most;
+    return n < 1 ? 1 : (int)n;
 }
 
 // ---- fan exchange (mpx_xfer_fan, k_xfer_fan) --------------------------------
@@ -292,12 +308,6 @@ inline int fan_default_nwg(long long block_len, bool same_device, int nranks) {
     const int cap = share < 1 ? 1 : share;
     const int n = bulk_nwg(block_len, same_device);
     return n < cap ? n : cap;
-}
-// at least kMinPushChunk bytes per workgroup, at least one workgroup
-inline int fan_narrow_nwg(int nwg, long long block_len) {
-    const long long most = (block_len + kMinPushChunk - 1) / kMinPushChunk;
-    const long long n = nwg < most ? nwg : most;
-    return n < 1 ? 1 : (int)n;
 }
 
 // Fills the host image of a rank's fan table for a call whose links have the

@@ -307,7 +307,7 @@ def test_armed_calls_across_the_token_wrap():
 
 def test_failed_launch_gives_every_counter_back(monkeypatch):
     """MPX_TEST=fail_launch=0 with rank 0's next token Q - 1, armed and
-    unarmed: unprepare_call gives the token and the call number back, so
+    unarmed: give_back gives the token and the call number back, so
     every counter is where it was; the next calls (tokens Q - 1 and Q) pass"""
     X = HostPairs(BULK_N + GUARD)
     try:

@@ -1,8 +1,9 @@
 // fan_host_check — the host arithmetic of the fan exchange, as a stand-alone
 // program for the host sanitizers (tools/asan_fan.sh builds it with
 // -fsanitize=address,undefined and runs it once; no GPU, no libmpx):
-//   * fan_default_nwg / fan_narrow_nwg / fan_build_map (mpx_internal.h): what
-//     mpx_xfer_fan builds its link table's widths and workgroup map with;
+//   * fan_default_nwg / link_nwg / fan_build_map (mpx_internal.h): what
+//     mpx_xfer_fan builds its link table's widths and workgroup map with, and
+//     link_nwg as the pair call's width rule too (prepare_call);
 //   * mpxh_fan_stride / mpxh_fan_bytes / mpxh_fan_peers (mpx_host.c): the
 //     block layout and peer lists of mpx_perf -m 1, and its -m validation.
 // Every property is checked against a restatement written here; the first
@@ -44,13 +45,47 @@ static int check_widths() {
                 const int cap = 128 / (nranks - 1) > 1 ? 128 / (nranks - 1) : 1;
                 REQUIRE(w >= 1 && w <= cap && w <= bulk_nwg(n, same != 0));
                 REQUIRE(w == cap || w == bulk_nwg(n, same != 0));
-                const int nw = fan_narrow_nwg(w, n);
+                const int nw = link_nwg(0, 0, w, n);
                 REQUIRE(nw >= 1 && nw <= w);
                 REQUIRE(nw == 1 || (long long)(nw - 1) * kMinPushChunk < n);   // every workgroup but the last: >= 1 KiB
                 // the default grid of a rank with every peer stays resident with its peers'
                 REQUIRE((long long)nw * (nranks - 1) <= 128);
             }
-    REQUIRE(fan_narrow_nwg(96, 98305) == 96 && fan_narrow_nwg(256, 0) == 1 && fan_narrow_nwg(200, 262144) == 200);
+    REQUIRE(link_nwg(96, 0, 1, 98305) == 96 && link_nwg(0, 256, 1, 0) == 1 && link_nwg(200, 7, 1, 262144) == 200);
+    return 0;
+}
+
+// The pair rule (prepare_call): the call's option, else MPX_PUSH_WG, else
+// bulk_nwg; more than kMaxPushWG is refused; then at most one workgroup per
+// kMinPushChunk bytes and at least one — restated here step by step, to hold
+// the shared link_nwg against.
+static int pair_width(int opt, int env, long long len, bool same) {
+    long long w = opt > 0 ? opt : env > 0 ? env : bulk_nwg(len, same);
+    if (w > kMaxPushWG) return 0;
+    const long long most = (len + kMinPushChunk - 1) / kMinPushChunk;
+    if (w > most) w = most;
+    if (w < 1) w = 1;
+    return (int)w;
+}
+
+static int check_pair_widths() {
+    const long long sizes[] = {0, 1, 15, 16, 17, 1023, 1024, 1025, 4097, 16384, 16385, 65555, 98305, 456131,
+                               1 << 20, 4 << 20, 0x7fffffff};
+    const int widths[] = {-1, 0, 1, 2, 7, 64, 128, 255, 256, 257, 4096, 0x7fffffff};
+    for (long long n : sizes)
+        for (int same = 0; same <= 1; ++same)
+            for (int opt : widths)
+                for (int env : widths) {
+                    const int w = link_nwg(opt, env, bulk_nwg(n, same != 0), n);
+                    REQUIRE(w == pair_width(opt, env, n, same != 0));
+                    const int chosen = opt > 0 ? opt : env > 0 ? env : bulk_nwg(n, same != 0);
+                    REQUIRE((w == 0) == (chosen > kMaxPushWG));           // refused, never narrowed, above 256
+                    REQUIRE(w == 0 || (w >= 1 && w <= chosen && w <= kMaxPushWG));
+                    REQUIRE(w <= 1 || (long long)(w - 1) * kMinPushChunk < n);
+                }
+    // the size rule alone is never narrowed above 16 KiB (its chunks are 16-32 KiB)
+    REQUIRE(link_nwg(0, 0, bulk_nwg(456131, true), 456131) == 28 && link_nwg(0, 0, bulk_nwg(456131, false), 456131) == 14);
+    REQUIRE(link_nwg(0, 0, bulk_nwg(4 << 20, true), 4 << 20) == 128 && link_nwg(64, 0, 128, 4097) == 5);
     return 0;
 }
 
@@ -129,7 +164,7 @@ static int check_host() {
 }
 
 int main() {
-    if (check_widths() || check_map() || check_host()) return 1;
+    if (check_widths() || check_pair_widths() || check_map() || check_host()) return 1;
     puts("fan_host_check: ok");
     return 0;
 }

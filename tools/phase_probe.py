@@ -6,10 +6,13 @@ shape; per call and side, mpx_last_phases splits the wall time into host
 preparation, launch -> kernel start, the wait for the peer's receives, the
 kernel and completion -> return.  Medians over the calls.
 
-    MPX_SYNC=query|event python tools/phase_probe.py [calls] [armed]
+    MPX_SYNC=query|event python tools/phase_probe.py [calls] [armed|fan]
 
 armed: every call is armed (mpx_xfer_arm) before the barrier and started
 after it, so its launch is outside the timed call.
+fan: instead of the pair shapes, three ranks on GPU 0 exchange a block with
+each other in one mpx_xfer_fan call each (the same phases, per rank).
+MPX_LIB names the libmpx.so to load (an A/B of two builds).
 """
 import json
 import os
@@ -26,6 +29,54 @@ ARMED = "armed" in sys.argv[2:]
 SHAPES = [("unidir", mpx.MODE_UNIDIR, 456131, 10), ("unidir", mpx.MODE_UNIDIR, 4 << 20, 10),
           ("pingpong", mpx.MODE_PINGPONG, 8, 10), ("unidir", mpx.MODE_UNIDIR, 4 << 20, 500)]
 CAP = 4 << 20
+FAN = "fan" in sys.argv[2:]
+FAN_RANKS, FAN_BLOCK, FAN_ITERS = 3, 65536, 10
+
+
+def fan_probe():
+    with mpx.Context(FAN_RANKS, "kernel") as c:
+        bufs = []
+        for r in range(FAN_RANKS):
+            tx, rx = c.alloc(0, FAN_RANKS * FAN_BLOCK), c.alloc(0, FAN_RANKS * FAN_BLOCK)
+            c.fill(tx, FAN_RANKS * FAN_BLOCK, mpx.FILL_SPLITMIX, r + 11)
+            c.attach(r, 0, tx, rx, FAN_RANKS * FAN_BLOCK)
+            bufs.append((tx, rx))
+        bar = threading.Barrier(FAN_RANKS)
+        rows = {r: [] for r in range(FAN_RANKS)}
+        errs = []
+
+        def side(r):
+            peers = [p for p in range(FAN_RANKS) if p != r]
+            try:
+                for k in range(CALLS + 2):
+                    bar.wait()
+                    t, _ = c.fan(r, peers, FAN_ITERS, bufs[r][0], bufs[r][1], FAN_BLOCK, FAN_BLOCK)
+                    if k >= 2:
+                        rows[r].append(dict(c.phases(r), device_s=t.device_s))
+            except Exception as e:  # noqa: BLE001
+                errs.append(f"rank {r}: {e}")
+                bar.abort()
+        th = [threading.Thread(target=side, args=(r,)) for r in range(FAN_RANKS)]
+        for x in th:
+            x.start()
+        for x in th:
+            x.join()
+        rec = dict(sync=os.environ.get("MPX_SYNC", "query"), armed=False, shape="fan", ranks=FAN_RANKS,
+                   bytes=FAN_BLOCK, iters=FAN_ITERS, calls=CALLS)
+        if errs:
+            rec["error"] = errs[:2]
+        else:
+            walls = [max(x[k]["wall_s"] for x in rows.values()) for k in range(CALLS)]
+            rec["pair_wall_us_median"] = round(statistics.median(walls) * 1e6, 2)
+            for r in range(FAN_RANKS):
+                rec[f"r{r}"] = {k: round(statistics.median(x[k] for x in rows[r]) * 1e6, 2) for k in rows[r][0]
+                                if k not in ("armed", "resident")}
+        print(json.dumps(rec), flush=True)
+
+
+if FAN:
+    fan_probe()
+    sys.exit(0)
 
 with mpx.Context(2, "kernel") as c:
     bufs = []
