@@ -111,7 +111,8 @@ typedef struct mpx_timing {
                                  next copy's loads in flight (k_copy_pipe),
                                  7 = bulk payloads pulled by the receiver
                                  (MPX_XFER_PULL), 8 = the SDMA engine's
-                                 pulled form, 9 = fan exchange (mpx_xfer_fan)   */
+                                 pulled form, 9 = fan exchange (mpx_xfer_fan),
+                                 10 = lock-step LL fan exchange (MPX_FAN_LL)    */
     int32_t check_failures;   /* iterations whose payload checksum mismatched  */
     uint64_t check_iters;     /* iterations whose payload was checksummed      */
     /* receive accounting, as the reference's loop completes receives: every
@@ -313,10 +314,34 @@ int mpx_xfer_ex(mpx_ctx *ctx, int mode, int my_group, int my_rank, int peer_rank
    check_iters and check_failures are summed over the links.  The link
    counters (mpx_link_counters) move as if each link had run a pair call.
    Fan calls are never traced by the latency recorder.  The ABI version is
-   unchanged: callers detect the feature by symbol. */
+   unchanged: callers detect the feature by symbol.
+
+     MPX_FAN_LL (mpx_fan_opts.flags): the same peers, layout and symmetric
+   peer sets, but per link a LOCK-STEP exchange of LL granules (data and tag
+   in the same 8 bytes, as the pair loops send below their LL threshold):
+   iteration i of a link pushes my block into the peer's LL row, waits until
+   the peer's push i has arrived in mine, unpacks it into
+   rx[peer * stride : + block_len) and only then starts iteration i + 1 —
+   MPI_Sendrecv with every peer, per iteration.  Links stay independent, so
+   mpx_fan_link.device_s / iters is that link's exchange latency.  Push
+   number s of a link lands in half s & 1 of the sender's LL row (double
+   buffered, no credits), hence block_len <= MPX_FAN_LL_MAX, half of the row.
+   Check mode checksums every unpacked block and poisons all but the last.
+   block_len = 0 is one empty granule per push; iters = 0 moves nothing.
+     One workgroup per link: nwg = 1 in mpx_timing and in every link record
+   (MPX_FAN_WG is ignored), protocol = 10; bytes, launches, recv_done, the
+   digests and the link counters are as for a bulk fan call.  Both ends of a
+   link must set the flag alike (as for nwg): a mismatch runs into the
+   bounded waits (MPX_ERR_TIMEOUT).  MPX_ERR_INVALID, before any GPU work:
+   block_len > MPX_FAN_LL_MAX, MPX_FAN_LL with MPX_XFER_STREAM (there are no
+   bulk stores to stream), any other flag bit, opts.nwg > 1.  The ABI version
+   stays 7: callers detect the flag by the define, and a library without it
+   answers MPX_ERR_INVALID. */
+#define MPX_FAN_LL 8          /* (a bit no mpx_xfer_opts flag uses)            */
+#define MPX_FAN_LL_MAX 4096   /* largest block_len of an MPX_FAN_LL call       */
 typedef struct mpx_fan_opts {
     int32_t check;            /* 1: checksum + poison every received block     */
-    int32_t flags;            /* 0 or MPX_XFER_STREAM                          */
+    int32_t flags;            /* 0, MPX_XFER_STREAM or MPX_FAN_LL              */
     uint32_t timeout_ms;      /* per-wait device deadline; 0 = default (10 s)  */
     int32_t nwg;              /* width of every link; 0 = automatic            */
     const uint64_t *expect_checksum; /* [npeers], check = 1: mpx_checksum() of

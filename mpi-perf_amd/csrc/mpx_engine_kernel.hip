@@ -496,7 +496,8 @@ int mpx_xfer_disarm(mpx_ctx* ctx, int my_rank) {
 }
 
 // ---------------------------------------------------------------------------
-// fan exchange (include/mpx.h mpx_xfer_fan; k_xfer_fan)
+// fan exchange (include/mpx.h mpx_xfer_fan; k_xfer_fan, and k_xfer_fan_ll for
+// MPX_FAN_LL)
 // ---------------------------------------------------------------------------
 namespace {
 // MPX_FAN_WG: every link's width (read per call; every rank of a job inherits
@@ -551,7 +552,9 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
     if ((long long)npeers * iters > 0x7fffffffll) return fail(MPX_ERR_INVALID, "npeers x iters %d x %d", npeers, iters);
     if (stride % 16 != 0 || stride < (size_t)block_len)
         return fail(MPX_ERR_INVALID, "stride %zu: a multiple of 16, at least block_len %d", stride, block_len);
-    if (opts && (opts->flags & ~MPX_XFER_STREAM)) return fail(MPX_ERR_INVALID, "flags %#x: only MPX_XFER_STREAM", opts->flags);
+    if (opts && (opts->flags & ~(MPX_XFER_STREAM | MPX_FAN_LL)))
+        return fail(MPX_ERR_INVALID, "flags %#x: only MPX_XFER_STREAM or MPX_FAN_LL", opts->flags);
+    const bool ll = opts && (opts->flags & MPX_FAN_LL);
     const bool check = opts && opts->check;
     if (check && !opts->expect_checksum) return fail(MPX_ERR_INVALID, "check mode needs expect_checksum[npeers]");
     bool seen[MPX_MAX_RANKS] = {};
@@ -571,13 +574,22 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
     if ((size_t)(top + 1) * stride > me.len)
         return fail(MPX_ERR_INVALID, "block %d at stride %zu lies past rank %d's attached length %zu", top, stride, my_rank,
                     me.len);
+    // MPX_FAN_LL: a lock-step exchange of LL granules, one workgroup per link
+    if (ll) {
+        if (block_len > MPX_FAN_LL_MAX)
+            return fail(MPX_ERR_INVALID, "MPX_FAN_LL: block_len %d above MPX_FAN_LL_MAX %d", block_len, MPX_FAN_LL_MAX);
+        if (opts->flags & MPX_XFER_STREAM)
+            return fail(MPX_ERR_INVALID, "MPX_FAN_LL with MPX_XFER_STREAM: an LL call has no bulk stores to stream");
+        if (opts->nwg > 1) return fail(MPX_ERR_INVALID, "MPX_FAN_LL: nwg %d (an LL link is one workgroup wide)", opts->nwg);
+    }
     int nwg[MPX_MAX_RANKS];
     for (int k = 0; k < npeers; ++k) {
         const Rank& peer = ctx->r[peers[k]];
         if ((size_t)(my_rank + 1) * stride > peer.len)
             return fail(MPX_ERR_INVALID, "block %d at stride %zu lies past rank %d's attached length %zu", my_rank, stride,
                         peers[k], peer.len);
-        nwg[k] = fan_link_nwg(opts ? opts->nwg : 0, block_len, same_device(me, peer), ctx->nranks);
+        // (MPX_FAN_WG is not read for an LL call: its width is 1 by definition)
+        nwg[k] = ll ? 1 : fan_link_nwg(opts ? opts->nwg : 0, block_len, same_device(me, peer), ctx->nranks);
         if (nwg[k] < 1) return fail(MPX_ERR_INVALID, "nwg > %d", kMaxPushWG);
     }
     std::vector<FanTable> image(1);
@@ -617,9 +629,9 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
     Call c;
     c.my_rank = my_rank;
     c.iters = iters;
-    c.kernel = "fan kernel";
+    c.kernel = ll ? "LL fan kernel" : "fan kernel";
     c.fail_launch = knobs.fail_launch == my_rank;
-    c.protocol = kProtoFan;
+    c.protocol = ll ? kProtoFanLL : kProtoFan;
     c.csum_words = check ? nsum : 0;
     c.table = &ht;
     // the call's numbers: the rank's token, and a call number on every link
@@ -642,7 +654,15 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
         if (nwg[k] > c.nwg) c.nwg = nwg[k];   // reported: the widest link
     }
     // ---- the shared steps: launch, completion, check-mode verdict ---------------
-    const int lst = launch_call(me, c, [&] { return launch_fan(a, grid, me.stream); });
+    FanLLArgs la{};   // (MPX_FAN_LL: the grid is npeers, workgroup k is link k)
+    if (ll) {
+        la.f = a;
+        if (knobs.lag_rank == my_rank && knobs.lag_us > 0) {
+            la.lag_link = knobs.lag_wg < 0 ? knobs.lag_wg + npeers : knobs.lag_wg;
+            la.lag_ticks = (u64)knobs.lag_us * 100ull;   // s_memrealtime: 100 MHz
+        }
+    }
+    const int lst = launch_call(me, c, [&] { return ll ? launch_fan_ll(la, me.stream) : launch_fan(a, grid, me.stream); });
     if (lst != MPX_OK) {
         give_back(me, c);
         return lst;
@@ -650,6 +670,11 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
     t->bytes = 2ull * (uint64_t)block_len * (uint64_t)iters * (uint64_t)npeers;
     Fin fin{};
     TRY(complete_call(me, c, peers, npeers, t_call, t, &fin, [&](unsigned iteration) {
+        if (ll)
+            return fail(MPX_ERR_TIMEOUT,
+                        "rank %d: a device wait of the lock-step LL fan exchange timed out at iteration %u (%d B with %d peers; "
+                        "both ends of a link must set MPX_FAN_LL alike)",
+                        my_rank, iteration, block_len, npeers);
         return fail(MPX_ERR_TIMEOUT, "rank %d: a device wait of the fan exchange timed out at iteration %u (%d B to %d peers)",
                     my_rank, iteration, block_len, npeers);
     }));

@@ -23,7 +23,7 @@ constexpr int kStageMaxBytes = 60 << 10; // LDS-staged tx chunk per workgroup, m
 
 // Protocol ids reported in mpx_timing.protocol
 enum Proto { kProtoLL = 0, kProtoBulk = 1, kProtoSdma = 2, kProtoRccl = 3, kProtoCopy = 4, kProtoCopySteps = 5,
-             kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8, kProtoFan = 9 };
+             kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8, kProtoFan = 9, kProtoFanLL = 10 };
 
 // One rank's receive mailbox, in that rank's HBM (uncached / fine-grained so a
 // poll sees stores that arrive over xGMI).  Written ONLY by the peers, polled
@@ -300,6 +300,18 @@ struct FanArgs {
     int check, stream, nb_publish, skip_push;
 };
 
+// The lock-step LL fan exchange (MPX_FAN_LL, k_xfer_fan_ll): one workgroup
+// per link, the grid is nlinks (no workgroup map).  Push number s of a link
+// lands in half s & 1 of the sender's LL row — kFanLLHalf granules each, so a
+// block is at most MPX_FAN_LL_MAX bytes (DESIGN.md "Fan exchange").
+constexpr int kFanLLHalf = kLLGranules / 2;
+static_assert(kFanLLHalf * 4 == MPX_FAN_LL_MAX, "a half of the LL row holds one MPX_FAN_LL block");
+struct FanLLArgs {
+    FanArgs f;                // stream and nb_publish unused; check picks the instantiation
+    int lag_link;             // test knob (MPX_TEST lag_wg): the link's workgroup that stalls
+    u64 lag_ticks;            //   lag_ticks between its push and its wait of iteration iters / 2; 0 = off
+};
+
 // Default width of a fan link: the pair rule, capped so that the kernels of
 // nranks ranks sharing one GPU (each up to nranks - 1 links wide) stay
 // resident together.  Only things both ends of a link see alike go in.
@@ -339,6 +351,7 @@ inline int fan_build_map(FanTable* tab, int nlinks, const int* nwg, int iters) {
 
 // Launchers implemented in mpx_kernels.hip
 hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s);
+hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s);   // grid = a.f.nlinks
 hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s);
 hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out);
 // all `iters` copies in one launch with a grid barrier between steps; *bar

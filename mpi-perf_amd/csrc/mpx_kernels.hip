@@ -8,6 +8,8 @@
 //               (do_mpi_benchmark*, /root/reference/mpi_perf.c:66-145)
 //   k_xfer_fan  one rank's blocks to and from several peers in one launch
 //               (mpx_xfer_fan): every workgroup owns one chunk of one link
+//   k_xfer_fan_ll  the same with MPX_FAN_LL: per link a lock-step exchange of
+//               LL granules, one workgroup per link
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -454,7 +456,9 @@ __global__ void k_seqbase(u64* base, u64 tx, u64 rx, int add) {
 // phase stamps of workgroup 0 (Loop::ts)
 enum { kTsEntry = 0, kTsPosted = 1, kTsFirst = 2, kTsLoop = 3 };
 
-template <int MODE>
+// ANYWG: every workgroup owns an LL message of its own (k_xfer_fan_ll: one
+// link per workgroup); false: a pair's LL message is workgroup 0's.
+template <int MODE, bool ANYWG = false>
 struct Loop {
     const XferArgs& a;
     int* s_abort;      // LDS: this workgroup gave up
@@ -465,7 +469,9 @@ struct Loop {
     // read-only while the loop runs (the reference re-sends the same buffer
     // every iteration, mpi_perf.c:72,80,135), so a send is stores only — no
     // tx load on the latency path.
-    u64 pre[kLLUnitsPerLane];
+    // 16-B LL units per lane: a pair's message fills the row, an LL fan's half of it
+    static constexpr int kUnits = ANYWG ? kLLUnitsPerLane / 2 : kLLUnitsPerLane;
+    u64 pre[kUnits];
     u64* s_seen = nullptr;   // LDS, pull mode: the peer's ready word as last read
     // a.stage: s_tx holds this workgroup's chunk once the first push (which
     // reads tx from memory and fills s_tx on the way) is done
@@ -476,7 +482,7 @@ struct Loop {
 
     __device__ void preload_ll(long long n) {
 #pragma unroll
-        for (int j = 0; j < kLLUnitsPerLane; ++j) {
+        for (int j = 0; j < kUnits; ++j) {
             const long long off = 8ll * ((int)threadIdx.x + j * kBlock);
             u64 w = 0;
             if (off + 8 <= n) {
@@ -489,6 +495,7 @@ struct Loop {
     }
 
     __device__ bool aborted() const { return *s_abort != 0; }
+    __device__ bool ll_owner() const { return ANYWG || blockIdx.x == 0; }
 
     // Record a timeout: LDS flag for this workgroup, device word for the
     // others (scratch[1]), host-mapped status for the host.
@@ -511,14 +518,16 @@ struct Loop {
     // ---- send: push n bytes of tx[0:n) into the peer's rx -------------------
     // LL: one workgroup; every 16-B store carries two granules {payload:32,
     // tag:32} (each 8-B half lands untorn), so 8 payload bytes per store.
-    __device__ void push_ll(long long n, u64 seq) const {
-        if (blockIdx.x != 0) return;
+    // goff: the granule of the peer's landing row the message starts at (the
+    // LL fan's half, kFanLLHalf * (seq & 1); a pair's message starts at 0).
+    __device__ void push_ll(long long n, u64 seq, unsigned goff = 0) const {
+        if (!ll_owner()) return;
         const int ng = n > 0 ? (int)((n + 3) >> 2) : 1;   // a 0-byte message is one empty granule
         const int nu = (ng + 1) >> 1;                      // 16-B units
         const unsigned tag = ll_tag(seq);
-        const __amdgpu_buffer_rsrc_t dst = rsrc(&a.peer_mb->ll[a.my_slot][0], (unsigned)(nu * 16));
+        const __amdgpu_buffer_rsrc_t dst = rsrc(&a.peer_mb->ll[a.my_slot][goff], (unsigned)(nu * 16));
 #pragma unroll
-        for (int j = 0; j < kLLUnitsPerLane; ++j) {
+        for (int j = 0; j < kUnits; ++j) {
             const int u = (int)threadIdx.x + j * kBlock;
             if (u < nu) {
                 const v4u v = {(unsigned)pre[j], tag, (unsigned)(pre[j] >> 32), tag};
@@ -614,12 +623,12 @@ struct Loop {
 
     // test knob: an LL message whose payload was "lost" — the tags arrive (so
     // the receiver completes), the data words carry a fixed wrong pattern
-    __device__ void push_ll_tags_only(long long n, u64 seq) const {
-        if (blockIdx.x != 0) return;
+    __device__ void push_ll_tags_only(long long n, u64 seq, unsigned goff = 0) const {
+        if (!ll_owner()) return;
         const int ng = n > 0 ? (int)((n + 3) >> 2) : 1;
         const int nu = (ng + 1) >> 1;
         const unsigned tag = ll_tag(seq);
-        const __amdgpu_buffer_rsrc_t dst = rsrc(&a.peer_mb->ll[a.my_slot][0], (unsigned)(nu * 16));
+        const __amdgpu_buffer_rsrc_t dst = rsrc(&a.peer_mb->ll[a.my_slot][goff], (unsigned)(nu * 16));
         for (int u = threadIdx.x; u < nu; u += kBlock) {
             const v4u v = {~0u, tag, ~0u, tag};
             __builtin_amdgcn_raw_buffer_store_b128(v, dst, (unsigned)u * 16, 0, kAuxSys);
@@ -634,36 +643,36 @@ struct Loop {
     // (the sender tags both halves of every unit).  Against the earlier 8-B
     // granule loads it halves the load count: 4 KiB ping-pong 4.32 -> 2.56 us
     // per iteration (profiles/r01_ll_ab.jsonl, r01_ll_preload_ab.jsonl).
-    __device__ bool wait_ll(long long n, u64 seq, int iter) const {
+    __device__ bool wait_ll(long long n, u64 seq, int iter, unsigned goff = 0) const {
         const int ng = n > 0 ? (int)((n + 3) >> 2) : 1;
         const int nu = (ng + 1) >> 1;
         const int mine = nu > (int)threadIdx.x ? (nu - (int)threadIdx.x + kBlock - 1) / kBlock : 0;
         const unsigned tag = ll_tag(seq);
-        const __amdgpu_buffer_rsrc_t src = rsrc(&a.my_mb->ll[a.peer_slot][0], (unsigned)(nu * 16));
-        v4u x[kLLUnitsPerLane];
+        const __amdgpu_buffer_rsrc_t src = rsrc(&a.my_mb->ll[a.peer_slot][goff], (unsigned)(nu * 16));
+        v4u x[kUnits];
         if (mine > 0) {
             const u64 t0 = now_ticks();
             u64 spins = 0;
             for (;;) {
 #pragma unroll
-                for (int j = 0; j < kLLUnitsPerLane; ++j)
+                for (int j = 0; j < kUnits; ++j)
                     if (j < mine)
                         x[j] = __builtin_amdgcn_raw_buffer_load_b128(src, ((unsigned)threadIdx.x + j * kBlock) * 16, 0,
                                                                      kAuxSysVol);
                 bool ok = true;
 #pragma unroll
-                for (int j = 0; j < kLLUnitsPerLane; ++j)
+                for (int j = 0; j < kUnits; ++j)
                     if (j < mine) ok &= (x[j].y == tag) & (x[j].w == tag);
                 if (ok) break;
                 if (should_stop(++spins, t0)) { give_up(iter); break; }
                 __builtin_amdgcn_s_sleep(0);
             }
-            if (blockIdx.x == 0 && !*s_abort) {
+            if (ll_owner() && !*s_abort) {
                 // write-through (sc0 sc1) like every other store into rx, so
                 // the bytes are in memory once the call's completion word is
                 const __amdgpu_buffer_rsrc_t rr = rsrc(a.rx, (unsigned)n);
 #pragma unroll
-                for (int j = 0; j < kLLUnitsPerLane; ++j) {
+                for (int j = 0; j < kUnits; ++j) {
                     if (j >= mine) break;
                     const long long off = 8ll * ((int)threadIdx.x + j * kBlock);
                     const u64 d = ((u64)x[j].z << 32) | x[j].x;
@@ -746,7 +755,7 @@ struct Loop {
             // unpacked by workgroup 0 with write-through stores: read back
             // the same way (sc0 sc1 loads: no L1 line of an earlier
             // iteration's read can serve them)
-            if (blockIdx.x == 0) {
+            if (ll_owner()) {
                 const __amdgpu_buffer_rsrc_t rr = rsrc(a.rx, (unsigned)n);
                 for (long long k = threadIdx.x; 8 * k < n; k += kBlock) {
                     const unsigned o = (unsigned)(8 * k);
@@ -1789,6 +1798,126 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
     L.finish_last();
 }
 
+// ---------------------------------------------------------------------------
+// k_xfer_fan_ll: the fan exchange with MPX_FAN_LL — per link a LOCK-STEP
+// exchange of LL granules (MPI_Sendrecv with every peer, per iteration).  The
+// grid is nlinks: workgroup k IS link k (no workgroup map) and runs the link's
+// whole loop alone, so no iteration of one link waits for another link.
+//   * post: the workgroup's first action is this call's number into the
+//     peer's Mailbox.posted; nothing is pushed before the peer's post is seen
+//     (once per call, as in k_xfer_fan);
+//   * preload: the link's tx block is read ONCE into VGPRs (Loop::preload_ll;
+//     <= 4096 B = 512 units, two per lane), so every push is stores only;
+//   * iteration i: push number s = tx_seq0 + i + 1 as LL units {lo, tag, hi,
+//     tag} into half s & 1 of the peer's ll[me] row (16-B sc0|sc1 buffer
+//     stores, no drain, no flag); poll half r & 1 of my ll[peer] row for the
+//     peer's push r = rx_seq0 + i + 1 (all of a lane's 16-B volatile loads
+//     back to back, both tags of each checked); unpack into the link's rx
+//     block with write-through stores; check mode then reads the block back
+//     (sc0 sc1), checksums it into csum[k * iters + i] and poisons all but
+//     the last (Loop::check's LL branch: the poison lands in my own rx, the
+//     peer writes only my LL row, so no credit).
+// Two halves suffice without credits: I push i + 1 only after I received the
+// peer's i; the peer pushed its i before it started to wait for my i, so it
+// may still be polling my i — which sits in the other half.  My i + 2 reuses
+// the half of my i and goes out only after I received the peer's i + 1, which
+// the peer issued only after its poll of my i had the data in registers
+// (DESIGN.md "Fan exchange").
+// Test knobs: skip_push = i — push i's tags arrive with a wrong payload;
+// lag — this link's workgroup stalls between its push and its wait of
+// iteration iters / 2, where a single-buffered zone would break.
+// Every wait is bounded (should_stop / give_up); the call ends as k_xfer_fan's
+// does.  Resource figures: DESIGN.md "Fan exchange".
+// ---------------------------------------------------------------------------
+template <bool CHECK>
+__global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan_ll(FanLLArgs q) {
+    __shared__ int s_abort;
+    __shared__ u64 lds4[4];
+    if (threadIdx.x == 0) s_abort = 0;
+    const FanArgs& f = q.f;
+    const int k = (int)blockIdx.x;
+    FanLink& lk = f.tab->link[k];
+    const long long n = f.len;
+    XferArgs x{};   // the link as a pair: what Loop's LL, wait and end-of-call helpers read
+    x.tx = f.tx + lk.off;
+    x.rx = f.rx + lk.off;
+    x.my_mb = f.my_mb;
+    x.peer_mb = lk.peer_mb;
+    x.my_slot = f.my_slot;
+    x.peer_slot = lk.peer;
+    x.status = f.status;
+    x.gbar = f.gbar;
+    x.csum = f.csum + lk.csum0;
+    x.timeout_ticks = f.timeout_ticks;
+    x.done_token = f.done_token;
+    x.iters = f.iters;
+    x.ll_max = MPX_FAN_LL_MAX;
+    Loop<MPX_MODE_PINGPONG, true> L{x, &s_abort, lds4, nullptr, {}};
+    __syncthreads();
+    L.stamp(kTsEntry);
+    const u64 tx0 = lk.tx_seq0, rx0 = lk.rx_seq0;
+    if (threadIdx.x == 0) st_sys(&lk.peer_mb->posted[f.my_slot], lk.call);
+    L.preload_ll(n);
+    bool ok = f.iters > 0;
+    if (ok) {
+        if (threadIdx.x == 0) {
+            const u64 t0 = now_ticks();
+            u64 spins = 0;
+            while (ld_sys(&f.my_mb->posted[lk.peer]) < lk.call) {
+                if (L.should_stop(++spins, t0)) { L.give_up(0); break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        __syncthreads();
+        ok = !L.aborted();
+    }
+    L.stamp(kTsPosted);
+    u64 done = 0;
+    for (int i = 0; ok && i < f.iters; ++i) {
+        const u64 s = tx0 + (u64)i + 1, r = rx0 + (u64)i + 1;
+        const unsigned out = (unsigned)(s & 1) * kFanLLHalf, in = (unsigned)(r & 1) * kFanLLHalf;
+        if (f.skip_push == i + 1) L.push_ll_tags_only(n, s, out);   // (test knob: this payload is "lost")
+        else L.push_ll(n, s, out);
+        if (q.lag_ticks && k == q.lag_link && i == f.iters / 2) {   // (test knob)
+            if (threadIdx.x == 0) {
+                const u64 t0 = now_ticks();
+                while (now_ticks() - t0 < q.lag_ticks) __builtin_amdgcn_s_sleep(127);
+            }
+            __syncthreads();
+        }
+        ok = L.wait_ll(n, r, i, in);
+        if (!ok) break;
+        ++done;
+        if constexpr (CHECK) L.check(n, i);
+    }
+    L.stamp(kTsLoop);
+    // the end of the link and of the call, as in k_xfer_fan
+    drain_stores();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_fetch_min(&lk.recv_done, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&lk.t_end, now_ticks(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!L.last_to_finish()) return;
+    // workgroup 0, every other workgroup done: the call's receive count and
+    // digest (of a call that completed: a timeout fails it anyway)
+    u64 part = 0, dpart = 0;
+    for (int j = threadIdx.x; j < f.nlinks; j += kBlock)
+        part += __hip_atomic_load(&f.tab->link[j].recv_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CHECK && !__hip_atomic_load(&f.gbar[kScrAbort], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        const u64 fmix = mix64((u64)n);
+        for (int j = threadIdx.x; j < f.nlinks * f.iters; j += kBlock)
+            dpart += __hip_atomic_load(&f.csum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ fmix;
+    }
+    const u64 d = block_sum(part, lds4);
+    const u64 g = block_sum(dpart, lds4);
+    if (threadIdx.x == 0) {
+        L.rdone = d;
+        L.rdig = g;
+    }
+    L.finish_last();
+}
+
 // stream engines' receive accounting (launch_account)
 __global__ __launch_bounds__(kBlock) void k_account(Status* st, const u64* csum, int j0, int count, u64 fmix) {
     __shared__ u64 lds4[4];
@@ -1851,6 +1980,14 @@ hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s) {
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
     void (*k)(FanArgs) = a.check ? k_xfer_fan<true> : k_xfer_fan<false>;
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s) {
+    if (a.f.nlinks < 1 || a.f.nlinks >= MPX_MAX_RANKS || a.f.len < 0 || a.f.len > MPX_FAN_LL_MAX) return hipErrorInvalidValue;
+    (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
+    void (*k)(FanLLArgs) = a.f.check ? k_xfer_fan_ll<true> : k_xfer_fan_ll<false>;
+    hipLaunchKernelGGL(k, dim3((unsigned)a.f.nlinks), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

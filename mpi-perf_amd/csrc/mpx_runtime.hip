@@ -209,7 +209,9 @@ CopyChoice copy_choice() {
 //   lag_wg=r:w:us   in non-blocking check mode, workgroup w of rank r (w < 0
 //                   counts from the last) stalls `us` before it checks the
 //                   call's last receive (pull mode: before it loads the call's
-//                   last payload), so that rank's call ends long after its peer's
+//                   last payload), so that rank's call ends long after its peer's;
+//                   in an MPX_FAN_LL call, link workgroup w of rank r stalls
+//                   between its push and its wait of iteration iters / 2
 //   no_posted       no receive-posted handshake (round 2's behaviour): the
 //                   negative control of tests/test_gpu_ordering.py
 //   no_pull_wait    pull mode: a sending side returns without waiting for the

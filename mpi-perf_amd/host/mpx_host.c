@@ -69,7 +69,8 @@ void mpxh_print_usage(FILE *f)
 		    -t <device wait timeout ms>\n\
 		    -A <launch each run's kernel before the barrier 0|1 (default 1)>\n\
 		    -L <raw-cap: record every iteration's latency, lat-*.csv (kernel engine, not -x 1)>\n\
-		    -m <1: every run is one fan exchange, each rank with all others at once (kernel engine)>\n");
+		    -m <1: every run is one fan exchange, each rank with all others at once (kernel engine)>\n\
+		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -147,37 +148,43 @@ int mpxh_fan_peers(int world, int rank, int *peers)
     return n;
 }
 
-/* -m 1 (a fan run) has no pair, no armed call, no recorder, one engine */
+/* -m 1 (a fan run) has no pair, no armed call, no recorder, one engine;
+   -m 2 (its lock-step LL form) the same, and blocks of at most MPXH_FAN_LL_MAX */
 static int validate_fan(const mpxh_options *o, int world, FILE *err)
 {
     const int top = o->sweep_min > 0 ? o->sweep_max : o->buff_sz;
+    const int m = o->fan == 2 ? 2 : 1;
     if (o->all_pairs) {
-        fprintf(err, "invalid -m 1 with -a 1: a fan run already has every rank exchange with all others\n");
+        fprintf(err, "invalid -m %d with -a 1: a fan run already has every rank exchange with all others\n", m);
         return 1;
     }
     if (o->arm_set && o->arm) {
-        fprintf(err, "invalid -m 1 with -A 1: a fan call cannot be armed ahead of the barrier\n");
+        fprintf(err, "invalid -m %d with -A 1: a fan call cannot be armed ahead of the barrier\n", m);
         return 1;
     }
     if (o->lat_cap >= 0) {
-        fprintf(err, "invalid -m 1 with -L %d: fan calls are never traced by the latency recorder\n", o->lat_cap);
+        fprintf(err, "invalid -m %d with -L %d: fan calls are never traced by the latency recorder\n", m, o->lat_cap);
         return 1;
     }
     if (o->engine != 0) {
-        fprintf(err, "invalid -m 1 with -e sdma|rccl: the fan exchange runs on the kernel engine only\n");
+        fprintf(err, "invalid -m %d with -e sdma|rccl: the fan exchange runs on the kernel engine only\n", m);
         return 1;
     }
     if (o->use_dotnet) {
-        fprintf(err, "invalid -m 1 with -d 1: the .NET launcher lines describe pairs\n");
+        fprintf(err, "invalid -m %d with -d 1: the .NET launcher lines describe pairs\n", m);
         return 1;
     }
     if (world < 2) {
-        fprintf(err, "invalid -m 1 with %d rank: a fan run needs at least 2\n", world);
+        fprintf(err, "invalid -m %d with %d rank: a fan run needs at least 2\n", m, world);
         return 1;
     }
     if (top < 0 || (top > 0 && mpxh_fan_bytes(world, top) == 0)) {
-        fprintf(err, "invalid -m 1 with -b %d: %d blocks of %zu bytes exceed the largest buffer a rank can attach\n", top,
+        fprintf(err, "invalid -m %d with -b %d: %d blocks of %zu bytes exceed the largest buffer a rank can attach\n", m, top,
                 world, mpxh_fan_stride(top));
+        return 1;
+    }
+    if (m == 2 && top > MPXH_FAN_LL_MAX) {
+        fprintf(err, "invalid -m 2 with -b %d: a lock-step LL fan block is at most %d bytes\n", top, MPXH_FAN_LL_MAX);
         return 1;
     }
     return 0;

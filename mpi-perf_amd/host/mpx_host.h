@@ -48,7 +48,8 @@ typedef struct mpxh_options {
                                            -1 (default) = off                */
     int fan;                        /* -m  1 = every run is one fan exchange of
                                            every rank with all the others
-                                           (mpx_xfer_fan)                     */
+                                           (mpx_xfer_fan); 2 = the same as a
+                                           lock-step LL exchange (MPX_FAN_LL) */
     int arm_set;                    /* -A was given on the command line       */
 } mpxh_options;
 
@@ -75,6 +76,8 @@ const char *mpxh_engine_name(int e);
 /* -m 1: blocks of a fan run lie `stride` apart in tx and rx: -b rounded up to
    4096 (the alignment mpx_alloc gives a buffer) */
 #define MPXH_FAN_ALIGN 4096
+/* -m 2: the largest -b (MPX_FAN_LL_MAX, include/mpx.h) */
+#define MPXH_FAN_LL_MAX 4096
 size_t mpxh_fan_stride(int buff_len);
 /* bytes of a fan run's tx (and rx): world blocks; 0 if that exceeds the
    largest length a rank can attach (2^31 - 1) or an argument is negative */
@@ -85,7 +88,8 @@ int mpxh_fan_peers(int world, int rank, int *peers);
 
 /* validate -L against -x / -e (the recorder traces the kernel engine's
    blocking loops only) and -m 1 against -a 1, an explicit -A 1, -L, -e, -d 1
-   and a -b too large for world blocks; then group_size, mpi_perf.c:399-403.
+   and a -b too large for world blocks (-m 2: the same, and a -b above
+   MPXH_FAN_LL_MAX); then group_size, mpi_perf.c:399-403.
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides
    by zero here (ppn == 0 in bidirectional mode): the caller raises SIGFPE. */

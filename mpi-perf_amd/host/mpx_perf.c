@@ -24,7 +24,8 @@
  * (one host) virtual host k = "<host>-<k>" for ranks [k*P, (k+1)*P).  With
  * -a 1 every run is one round of the circle-method all-pairs schedule; with
  * -m 1 every run is one fan exchange: every rank with all the others at once
- * (mpx_xfer_fan, kernel engine), any world >= 2.
+ * (mpx_xfer_fan, kernel engine), any world >= 2; -m 2 the same as a lock-step
+ * exchange of LL granules (MPX_FAN_LL, -b up to 4096).
  *
  * Built with -DMPX_WINDOWS_CLI (bin/mpx_perf_win), the front end is the
  * Windows / MS-MPI variant's (/root/reference/windows/mpi-perf.cpp):
@@ -421,6 +422,7 @@ static void *rank_main(void *arg)
    The run loop, timing, records and log rotation are rank_main's; there are
    no groups, so every rank writes its record (VMCount = world, NumOfFlows =
    world - 1, LocalIP = RemoteIP) and one gpu-*.csv line per link. */
+_Static_assert(MPXH_FAN_LL_MAX == MPX_FAN_LL_MAX, "-m 2's -b limit is the library's");
 static uint64_t fansum_of[MPXH_MAX_RANKS][MPXH_MAX_RANKS]; /* [src][dst]: checksum of src's block for dst */
 
 static void share_fan_checksums(int r, const uint64_t *mine)
@@ -459,6 +461,7 @@ static void *rank_main_fan(void *arg)
             uint64_t expect[MPXH_MAX_RANKS] = {0};
             memset(&fo, 0, sizeof fo);
             fo.timeout_ms = (uint32_t)opt.timeout_ms;
+            if (opt.fan == 2) fo.flags = MPX_FAN_LL; /* -m 2: per link a lock-step exchange of LL granules */
             if (opt.check) {
                 /* the world x world block checksums, read after every fill */
                 uint64_t mine[MPXH_MAX_RANKS] = {0};
@@ -490,7 +493,8 @@ static void *rank_main_fan(void *arg)
                     const double gbps = my_time > 0 ? 2.0 * B * opt.iters / my_time / 1e9 : 0.0;
                     fprintf(files.gpu_fp, "%s,%s,%d,%s,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%.3f,%s,%d,%llu,%d,%lld,%llu,%llu,%s,%s\n", ts,
                             opt.uuid, r, mpxh_engine_name(opt.engine), MPX_MODE_NONBLOCKING, dev_of[r], l->peer,
-                            dev_of[l->peer], B, opt.iters, my_time * 1e3, l->device_s * 1e3, gbps, "fan", l->nwg,
+                            dev_of[l->peer], B, opt.iters, my_time * 1e3, l->device_s * 1e3, gbps,
+                            tm.protocol == 10 ? "fan_ll" : "fan", l->nwg,
                             (unsigned long long)(opt.check ? opt.iters : 0), l->check_failures, run_idx,
                             (unsigned long long)l->recv_done, (unsigned long long)l->recv_digest, "inline", "");
                 }
@@ -825,7 +829,9 @@ int main(int argc, char **argv)
         }
     }
     if (opt.fan) {
-        if (is_root()) fprintf(stderr, "FAN: each of %d ranks exchanges with its %d peers in one launch\n", world, world - 1);
+        if (is_root())
+            fprintf(stderr, "FAN: each of %d ranks exchanges with its %d peers in one launch%s\n", world, world - 1,
+                    opt.fan == 2 ? " (lock-step LL)" : "");
     } else if (!opt.all_pairs && !win_cli) {
         for (int r = 0; r < world; ++r) {
             if (procs && r != me) continue; /* every rank prints its own line, mpi_perf.c:460-461 */

@@ -31,6 +31,9 @@ FILL_BYTE, FILL_SPLITMIX = 0, 1
 XFER_STREAM = 1
 XFER_PULL = 2
 XFER_NOSTAGE = 4
+XFER_FAN_LL = 8      # MPX_FAN_LL (mpx_fan_opts.flags): the lock-step LL fan exchange
+FAN_LL_MAX = 4096    # MPX_FAN_LL_MAX: its largest block_len
+PROTO_FAN_LL = 10    # mpx_timing.protocol of such a call
 ABI_VERSION = 7
 PATTERN_SEED = 0x6D70695F70657266
 MAX_RANKS = 64
@@ -376,18 +379,21 @@ class Context:
         return t
 
     def fan(self, my_rank: int, peers, iters: int, tx: Buffer, rx: Buffer, block_len: int, stride: int,
-            check_payload: bool = False, expect=None, timeout_ms: int = 0, nwg: int = 0, stream: bool = False):
+            check_payload: bool = False, expect=None, timeout_ms: int = 0, nwg: int = 0, stream: bool = False,
+            ll: bool = False):
         """mpx_xfer_fan: my_rank exchanges block_len bytes with every rank of
         `peers` in one launch (block j of tx / rx at j * stride).  expect:
         check mode, the checksum of each peer's block for my_rank, in the
-        order of `peers`.  Returns (Timing, [link dicts]); a failing call
+        order of `peers`.  ll: MPX_FAN_LL, per link a lock-step exchange of LL
+        granules (block_len <= FAN_LL_MAX).  Returns (Timing, [link dicts]); a failing call
         raises MpxError carrying .timing and .links as far as they were
         filled."""
         peers = list(peers)
         n = len(peers)
         arr = (C.c_int * max(n, 1))(*peers)
         exp = (C.c_uint64 * max(n, 1))(*(list(expect) if expect is not None else [0] * n))
-        o = FanOpts(check=1 if check_payload else 0, flags=XFER_STREAM if stream else 0, timeout_ms=timeout_ms,
+        flags = (XFER_STREAM if stream else 0) | (XFER_FAN_LL if ll else 0)
+        o = FanOpts(check=1 if check_payload else 0, flags=flags, timeout_ms=timeout_ms,
                     nwg=nwg, expect_checksum=C.cast(exp, C.POINTER(C.c_uint64)))
         t = Timing()
         links = (FanLink * max(n, 1))()

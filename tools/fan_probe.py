@@ -16,6 +16,21 @@ it.  It says what the two call shapes cost the GPU, sets no pass mark and
 feeds no headline.
 
     python tools/fan_probe.py [--repeats 5] [--iters 50] [--bytes 4194304] [--ranks 2,4,8]
+
+--ll: the lock-step LL fan exchange (MPX_FAN_LL) instead.  Per N and per block
+of 8 B, 256 B, 2 KiB and 4 KiB, one JSON line with the time per iteration
+(the slowest link's device_s / iters, the kernel's own clock; iterations
+chosen so that a call lasts at least 10 ms; best of `--repeats`) of
+
+    ll_fan        every rank one LL fan call with all others
+    checked_bulk  the bulk fan in check mode at the same size: the only
+                  lock-step fan there was before the flag (it pays a checksum,
+                  poison stores and a credit round trip per iteration)
+
+and, once per N, the 8-byte pair ping-pong's half round trip between ranks 0
+and 1.  Loopback figures as above: no link is in them, no pass mark.
+
+    python tools/fan_probe.py --ll [--repeats 5] [--ranks 2,4,8] > profiles/fan_ll_loopback.jsonl
 """
 import argparse
 import json
@@ -28,6 +43,7 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--bytes", type=int, default=4 << 20)
 ap.add_argument("--ranks", default="2,4,8")
+ap.add_argument("--ll", action="store_true")
 args = ap.parse_args()
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-perf_amd"))
 import mpx  # noqa: E402
@@ -58,6 +74,71 @@ def together(n, fn):
         raise RuntimeError("; ".join(errs))
     return out
 
+
+LL_BLOCKS = (8, 256, 2048, 4096)
+LL_CALL_S = 0.010
+
+
+def ll_probe(n):
+    """one JSON line per block size: the LL fan against the checked bulk fan"""
+    stride = 4096
+    with mpx.Context(n, "kernel") as c:
+        bufs = []
+        for r in range(n):
+            tx, rx = c.alloc(0, n * stride), c.alloc(0, n * stride)
+            c.fill(tx, n * stride, mpx.FILL_SPLITMIX, r + 11)
+            c.attach(r, 0, tx, rx, n * stride)
+            bufs.append((tx, rx))
+        peers = {r: [p for p in range(n) if p != r] for r in range(n)}
+
+        def per_iter(fn, iters):
+            """the slowest link's device_s / iters of one call of every rank"""
+            res = together(n, lambda r: fn(r, iters))
+            return max(l["device_s"] for _, links in res.values() for l in links) / iters
+
+        def best(fn):
+            iters = 200                                                # warm-up, then the call length: a short
+            for _ in range(3):                                         # call is mostly the wait for the peers' launch
+                t = per_iter(fn, iters)
+                if t * iters >= LL_CALL_S:
+                    break
+                iters = int(min(200000, max(iters, LL_CALL_S / max(t, 1e-9) * 1.2)))
+            return min(per_iter(fn, iters) for _ in range(args.repeats)), iters
+
+        def pingpong(r, iters):
+            return c.xfer(mpx.MODE_PINGPONG, 1 if r == 0 else 0, r, 1 - r, iters, bufs[r][0], bufs[r][1], 8,
+                          timeout_ms=20000)
+
+        def pair_half_rtt():
+            def once(iters):
+                res = together(2, lambda r: pingpong(r, iters))
+                return max(t.device_s for t in res.values()) / iters / 2
+            iters = 200
+            for _ in range(3):
+                t = once(iters)
+                if 2 * t * iters >= LL_CALL_S:
+                    break
+                iters = int(min(200000, max(iters, LL_CALL_S / max(2 * t, 1e-9) * 1.2)))
+            return min(once(iters) for _ in range(args.repeats)), iters
+
+        half, half_iters = pair_half_rtt()
+        for b in LL_BLOCKS:
+            sums = {r: [c.checksum(bufs[p][0], b, r * stride) for p in peers[r]] for r in range(n)}
+            ll, ll_iters = best(lambda r, it: c.fan(r, peers[r], it, bufs[r][0], bufs[r][1], b, stride, timeout_ms=20000,
+                                                    ll=True))
+            ck, ck_iters = best(lambda r, it: c.fan(r, peers[r], it, bufs[r][0], bufs[r][1], b, stride, timeout_ms=20000,
+                                                    check_payload=True, expect=sums[r]))
+            print(json.dumps(dict(
+                kind="loopback (one GPU, no link in it; no pass mark, no headline)", ranks=n, links_per_rank=n - 1,
+                block_bytes=b, repeats=args.repeats, ll_fan_us_per_iter=round(ll * 1e6, 3), ll_fan_iters=ll_iters,
+                checked_bulk_fan_us_per_iter=round(ck * 1e6, 3), checked_bulk_fan_iters=ck_iters,
+                pair_pingpong_8B_half_rtt_us=round(half * 1e6, 3), pair_pingpong_iters=half_iters)), flush=True)
+
+
+if args.ll:
+    for n in (int(x) for x in args.ranks.split(",")):
+        ll_probe(n)
+    sys.exit(0)
 
 for n in (int(x) for x in args.ranks.split(",")):
     if n >= 8:
