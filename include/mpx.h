@@ -313,7 +313,8 @@ int mpx_xfer_ex(mpx_ctx *ctx, int mode, int my_group, int my_rank, int peer_rank
    widest link, protocol = 9, recv_done = npeers * iters; recv_digest,
    check_iters and check_failures are summed over the links.  The link
    counters (mpx_link_counters) move as if each link had run a pair call.
-   Fan calls are never traced by the latency recorder.  The ABI version is
+   Fan calls are never traced by the latency recorder (MPX_FAN_LL calls have
+   a recorder of their own, per link: mpx_fan_lat_*).  The ABI version is
    unchanged: callers detect the feature by symbol.
 
      MPX_FAN_LL (mpx_fan_opts.flags): the same peers, layout and symmetric
@@ -478,6 +479,13 @@ int mpx_lat_get(mpx_ctx *ctx, int rank, mpx_lat *out);
 /* the last traced call's stamps t[0 .. min(iters, raw_cap)], at most `cap` of
    them, into stamps[]; *n = how many were written (0 before any traced call) */
 int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
+
+/* ---- per-link latency distribution of the lock-step LL fan exchange ------- */
+/* The link recorder: what mpx_lat_* is to a rank's pair calls, per LINK of a
+   rank's MPX_FAN_LL calls, in mpx_lat as it is.  Its five functions and
+   MPX_FAN_LAT_RAW_MAX are declared, with their contract, in a header of their
+   own, which is part of this one. */
+#include "mpx_fan_lat.h"
 
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of

@@ -661,6 +661,9 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
             la.lag_link = knobs.lag_wg < 0 ? knobs.lag_wg + npeers : knobs.lag_wg;
             la.lag_ticks = (u64)knobs.lag_us * 100ull;   // s_memrealtime: 100 MHz
         }
+        // the link recorder (mpx_fan_lat_enable): launch_fan_ll then picks the traced kernels
+        la.lat = me.fan_lat_on ? me.fan_lat : nullptr;
+        la.lat_stride = lat_block_bytes(me.fan_lat_cap);
     }
     const int lst = launch_call(me, c, [&] { return ll ? launch_fan_ll(la, me.stream) : launch_fan(a, grid, me.stream); });
     if (lst != MPX_OK) {

@@ -150,7 +150,9 @@ __host__ __device__ inline int ring_slot(int j, int iters, int slots) { return (
 // between calls, on the rank's stream (reset).  The block is allocated with
 // room for raw_cap + 1 stamps behind it, and raw_cap stands in the block
 // itself: the kernel bounds its raw stores by the very word the allocation
-// was sized with.
+// was sized with.  The link recorder (mpx_fan_lat_enable) is nranks such
+// blocks, one per peer rank, each written by lane 0 of that link's workgroup
+// of the rank's traced LL fan calls (k_xfer_fan_ll_lat; FanLLArgs.lat).
 struct LatBlock {
     u64 count, calls, min_ticks, max_ticks, sum_ticks, max_iter, last_iters;   // mpx_lat's, accumulated
     u64 raw_cap;            // iterations of a call whose end stamp is kept (host, at enable)
@@ -310,6 +312,12 @@ struct FanLLArgs {
     FanArgs f;                // stream and nb_publish unused; check picks the instantiation
     int lag_link;             // test knob (MPX_TEST lag_wg): the link's workgroup that stalls
     u64 lag_ticks;            //   lag_ticks between its push and its wait of iteration iters / 2; 0 = off
+    // the rank's link recorder (mpx_fan_lat_enable): nranks LatBlocks lat_stride
+    // bytes apart (lat_block_bytes(raw_cap)), link k's at lat + peer * lat_stride —
+    // keyed by the peer's rank, each written only by that link's workgroup.
+    // null = tracing off, and then no _lat kernel is launched
+    unsigned char* lat;
+    u64 lat_stride;
 };
 
 // Default width of a fan link: the pair rule, capped so that the kernels of

@@ -9,7 +9,8 @@
 //   k_xfer_fan  one rank's blocks to and from several peers in one launch
 //               (mpx_xfer_fan): every workgroup owns one chunk of one link
 //   k_xfer_fan_ll  the same with MPX_FAN_LL: per link a lock-step exchange of
-//               LL granules, one workgroup per link
+//               LL granules, one workgroup per link (k_xfer_fan_ll_lat: traced
+//               per link, mpx_fan_lat_*)
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -1236,20 +1237,22 @@ __device__ __forceinline__ u64 lat_stamp() {
     return t;
 }
 
-template <bool LAT>
+// ANYWG: lane 0 of EVERY workgroup traces, into a block of its workgroup's own
+// (k_xfer_fan_ll_lat: workgroup k is link k); false: workgroup 0's lane 0 only.
+template <bool LAT, bool ANYWG = false>
 struct LatTrace {
     __device__ bool on() const { return false; }
     __device__ void begin(LatBlock*, u64, u64, int) {}
     __device__ u64 tick(int) { return 0; }
     __device__ void end() {}
 };
-template <>
-struct LatTrace<true> {
+template <bool ANYWG>
+struct LatTrace<true, ANYWG> {
     LatBlock* blk = nullptr;
     u64 prev = 0, mn = ~0ull, mx = 0;   // (the sum telescopes: prev - t[0], taken at the end)
     unsigned cap = 0, maxi = 0, n = 0;
 
-    __device__ bool on() const { return blockIdx.x == 0 && threadIdx.x == 0; }
+    __device__ bool on() const { return (ANYWG || blockIdx.x == 0) && threadIdx.x == 0; }
     // t[0]: the instant mpx_phases.first_iter_s counts from (complete_call's
     // t_go): the peer's post on a side that pushes first, else the entry
     __device__ __forceinline__ void begin(LatBlock* b, u64 t_entry, u64 t_posted, int iters) {
@@ -1828,6 +1831,12 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
 // iteration iters / 2, where a single-buffered zone would break.
 // Every wait is bounded (should_stop / give_up); the call ends as k_xfer_fan's
 // does.  Resource figures: DESIGN.md "Fan exchange".
+// k_xfer_fan_ll_lat (below) is the traced form (mpx_fan_lat_*; LatTrace<true,
+// true>): lane 0 of EVERY workgroup is a tracer, into the block of its link's
+// peer (q.lat + peer * q.lat_stride).  t[0] is a clock read of the link's own
+// behind the posted wait (Loop::stamp records workgroup 0 only, for the Fin
+// line); t[i + 1] is read at the bottom of iteration i, behind wait_ll and
+// the check.  The fold (end) comes before the workgroup counts itself out.
 // ---------------------------------------------------------------------------
 template <bool CHECK>
 __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan_ll(FanLLArgs q) {
@@ -1891,6 +1900,107 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
         if constexpr (CHECK) L.check(n, i);
     }
     L.stamp(kTsLoop);
+    // the end of the link and of the call, as in k_xfer_fan
+    drain_stores();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_fetch_min(&lk.recv_done, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&lk.t_end, now_ticks(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!L.last_to_finish()) return;
+    // workgroup 0, every other workgroup done: the call's receive count and
+    // digest (of a call that completed: a timeout fails it anyway)
+    u64 part = 0, dpart = 0;
+    for (int j = threadIdx.x; j < f.nlinks; j += kBlock)
+        part += __hip_atomic_load(&f.tab->link[j].recv_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CHECK && !__hip_atomic_load(&f.gbar[kScrAbort], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        const u64 fmix = mix64((u64)n);
+        for (int j = threadIdx.x; j < f.nlinks * f.iters; j += kBlock)
+            dpart += __hip_atomic_load(&f.csum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ fmix;
+    }
+    const u64 d = block_sum(part, lds4);
+    const u64 g = block_sum(dpart, lds4);
+    if (threadIdx.x == 0) {
+        L.rdone = d;
+        L.rdig = g;
+    }
+    L.finish_last();
+}
+
+// k_xfer_fan_ll_lat: k_xfer_fan_ll with the link recorder (see above).  A copy
+// of its own, not a shared body: sharing one changed the untraced kernels'
+// register allocation, and those stay instruction for instruction what they
+// were (k_xfer_fan keeps its own end-of-call code for the same reason).  Keep
+// the two in step.
+template <bool CHECK>
+__global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan_ll_lat(FanLLArgs q) {
+    __shared__ int s_abort;
+    __shared__ u64 lds4[4];
+    if (threadIdx.x == 0) s_abort = 0;
+    const FanArgs& f = q.f;
+    const int k = (int)blockIdx.x;
+    FanLink& lk = f.tab->link[k];
+    const long long n = f.len;
+    XferArgs x{};   // the link as a pair: what Loop's LL, wait and end-of-call helpers read
+    x.tx = f.tx + lk.off;
+    x.rx = f.rx + lk.off;
+    x.my_mb = f.my_mb;
+    x.peer_mb = lk.peer_mb;
+    x.my_slot = f.my_slot;
+    x.peer_slot = lk.peer;
+    x.status = f.status;
+    x.gbar = f.gbar;
+    x.csum = f.csum + lk.csum0;
+    x.timeout_ticks = f.timeout_ticks;
+    x.done_token = f.done_token;
+    x.iters = f.iters;
+    x.ll_max = MPX_FAN_LL_MAX;
+    Loop<MPX_MODE_PINGPONG, true> L{x, &s_abort, lds4, nullptr, {}};
+    __syncthreads();
+    L.stamp(kTsEntry);
+    const u64 tx0 = lk.tx_seq0, rx0 = lk.rx_seq0;
+    if (threadIdx.x == 0) st_sys(&lk.peer_mb->posted[f.my_slot], lk.call);
+    L.preload_ll(n);
+    bool ok = f.iters > 0;
+    if (ok) {
+        if (threadIdx.x == 0) {
+            const u64 t0 = now_ticks();
+            u64 spins = 0;
+            while (ld_sys(&f.my_mb->posted[lk.peer]) < lk.call) {
+                if (L.should_stop(++spins, t0)) { L.give_up(0); break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        __syncthreads();
+        ok = !L.aborted();
+    }
+    L.stamp(kTsPosted);
+    LatTrace<true, true> T;
+    if (T.on()) {   // t[0]: this link's own read, behind its own posted wait
+        const u64 t = lat_stamp();
+        T.begin(reinterpret_cast<LatBlock*>(q.lat + (u64)lk.peer * q.lat_stride), t, t, f.iters);
+    }
+    u64 done = 0;
+    for (int i = 0; ok && i < f.iters; ++i) {
+        const u64 s = tx0 + (u64)i + 1, r = rx0 + (u64)i + 1;
+        const unsigned out = (unsigned)(s & 1) * kFanLLHalf, in = (unsigned)(r & 1) * kFanLLHalf;
+        if (f.skip_push == i + 1) L.push_ll_tags_only(n, s, out);   // (test knob: this payload is "lost")
+        else L.push_ll(n, s, out);
+        if (q.lag_ticks && k == q.lag_link && i == f.iters / 2) {   // (test knob)
+            if (threadIdx.x == 0) {
+                const u64 t0 = now_ticks();
+                while (now_ticks() - t0 < q.lag_ticks) __builtin_amdgcn_s_sleep(127);
+            }
+            __syncthreads();
+        }
+        ok = L.wait_ll(n, r, i, in);
+        if (!ok) break;
+        ++done;
+        if constexpr (CHECK) L.check(n, i);
+        if (T.on()) T.tick(i);   // one clock read: the bottom of iteration i
+    }
+    L.stamp(kTsLoop);
+    T.end();   // (before the drain: the fold's stores are out when the workgroup counts itself out)
     // the end of the link and of the call, as in k_xfer_fan
     drain_stores();
     __syncthreads();
@@ -1986,7 +2096,10 @@ hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s) {
 hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s) {
     if (a.f.nlinks < 1 || a.f.nlinks >= MPX_MAX_RANKS || a.f.len < 0 || a.f.len > MPX_FAN_LL_MAX) return hipErrorInvalidValue;
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
-    void (*k)(FanLLArgs) = a.f.check ? k_xfer_fan_ll<true> : k_xfer_fan_ll<false>;
+    // the link recorder on (a.lat): the traced instantiations
+    if (a.lat && a.lat_stride < sizeof(LatBlock)) return hipErrorInvalidValue;
+    void (*k)(FanLLArgs) = a.lat ? (a.f.check ? k_xfer_fan_ll_lat<true> : k_xfer_fan_ll_lat<false>)
+                                 : (a.f.check ? k_xfer_fan_ll<true> : k_xfer_fan_ll<false>);
     hipLaunchKernelGGL(k, dim3((unsigned)a.f.nlinks), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }

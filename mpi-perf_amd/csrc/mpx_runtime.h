@@ -169,6 +169,11 @@ struct Rank {
     int lat_alloc = 0;             //   raw_cap the block was allocated for
     int lat_cap = 0;               //   raw_cap in force
     bool lat_on = false;           //   blocking calls of this rank are traced
+    unsigned char* fan_lat = nullptr;   // link recorder (mpx_fan_lat_enable): ctx->nranks LatBlocks in device
+                                   //   memory, lat_block_bytes(fan_lat_cap) apart, keyed by peer rank
+    int fan_lat_alloc = 0;         //   raw_cap the blocks were allocated for
+    int fan_lat_cap = 0;           //   raw_cap in force (the blocks' stride)
+    bool fan_lat_on = false;       //   MPX_FAN_LL calls of this rank are traced per link
     FanTable* fan_tab = nullptr;   // fan exchange (mpx_xfer_fan): the link table in device memory
     FanTable* fan_host = nullptr;  //   and its pinned host image (allocated on the first fan call)
     u64 tx_seq[MPX_MAX_RANKS] = {};

@@ -594,6 +594,7 @@ int mpx_finalize(mpx_ctx* ctx) {
         if (rk.scratch) (void)hipFree(rk.scratch);
         if (rk.csum) (void)hipFree(rk.csum);
         if (rk.lat) (void)hipFree(rk.lat);
+        if (rk.fan_lat) (void)hipFree(rk.fan_lat);
         if (rk.fan_tab) (void)hipFree(rk.fan_tab);
         if (rk.fan_host) (void)hipHostFree(rk.fan_host);
         for (void* q : rk.retired) (void)hipFree(q);
@@ -837,6 +838,7 @@ void release_rank(Rank& rk) {
     if (rk.scratch) (void)hipFree(rk.scratch);
     if (rk.csum) (void)hipFree(rk.csum);
     if (rk.lat) (void)hipFree(rk.lat);
+    if (rk.fan_lat) (void)hipFree(rk.fan_lat);
     if (rk.fan_tab) (void)hipFree(rk.fan_tab);
     if (rk.fan_host) (void)hipHostFree(rk.fan_host);
     for (void* q : rk.retired) (void)hipFree(q);
@@ -1328,6 +1330,136 @@ int mpx_lat_raw(mpx_ctx* ctx, int rank, uint64_t* stamps, int cap, int* n) {
     if (have > (u64)cap) have = (u64)cap;
     if (have) {
         HIPCK(hipMemcpyAsync(stamps, me->lat->raw, (size_t)have * sizeof(u64), hipMemcpyDeviceToHost, me->stream));
+        HIPCK(hipStreamSynchronize(me->stream));
+    }
+    *n = (int)have;
+    return MPX_OK;
+}
+
+// ---- per-link latency recorder of the LL fan exchange (include/mpx.h) -------
+namespace {
+// lat_rank's rules (local, no armed call), with this recorder's codes: a rank
+// that is not local is MPX_ERR_INVALID here.
+int fan_lat_rank(mpx_ctx* ctx, int rank, Rank** out) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
+    if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) return fail(MPX_ERR_INVALID, "rank %d is not a local rank", rank);
+    if (ctx->r[rank].armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", rank);
+    *out = &ctx->r[rank];
+    return MPX_OK;
+}
+int fan_lat_peer(const mpx_ctx* ctx, int rank, int peer) {
+    if (peer < 0 || peer >= ctx->nranks || peer == rank) return fail(MPX_ERR_INVALID, "rank %d: peer rank %d", rank, peer);
+    return MPX_OK;
+}
+size_t fan_lat_stride(const Rank& me) { return lat_block_bytes(me.fan_lat_cap); }
+LatBlock* fan_lat_block(const Rank& me, int peer) {
+    return reinterpret_cast<LatBlock*>(me.fan_lat + (size_t)peer * fan_lat_stride(me));
+}
+// Every peer's block: statistics, histogram and raw count back to zero,
+// raw_cap in force (lat_clear, once per block).
+int fan_lat_clear(const mpx_ctx* ctx, Rank& me) {
+    LatBlock h{};
+    h.raw_cap = (u64)me.fan_lat_cap;
+    for (int p = 0; p < ctx->nranks; ++p)
+        HIPCK(hipMemcpyAsync(fan_lat_block(me, p), &h, offsetof(LatBlock, raw), hipMemcpyHostToDevice, me.stream));
+    HIPCK(hipStreamSynchronize(me.stream));
+    return MPX_OK;
+}
+int fan_lat_header(Rank& me, int peer, LatBlock* h) {
+    HIPCK(hipMemcpyAsync(h, fan_lat_block(me, peer), offsetof(LatBlock, raw), hipMemcpyDeviceToHost, me.stream));
+    HIPCK(hipStreamSynchronize(me.stream));
+    return MPX_OK;
+}
+}  // namespace
+
+int mpx_fan_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
+    if (ctx->engine != MPX_ENGINE_KERNEL)
+        return fail(MPX_ERR_UNSUPPORTED, "the link recorder runs inside the kernel engine's LL fan loop: not this engine");
+    Rank* me = nullptr;
+    TRY(fan_lat_rank(ctx, rank, &me));
+    if (raw_cap < 0 || raw_cap > MPX_FAN_LAT_RAW_MAX)
+        return fail(MPX_ERR_INVALID, "raw_cap %d not in [0,%d]", raw_cap, MPX_FAN_LAT_RAW_MAX);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    if (!me->fan_lat || me->fan_lat_alloc < raw_cap) {
+        // (no hipFree here: it waits for the whole device, ensure_csum)
+        const size_t bytes = (size_t)ctx->nranks * lat_block_bytes(raw_cap);
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            return fail(MPX_ERR_NOMEM, "link recorder of %zu B on device %d", bytes, me->dev);
+        }
+        HIPCK(e);
+        if (me->fan_lat) me->retired.push_back(me->fan_lat);
+        me->fan_lat = static_cast<unsigned char*>(p);
+        me->fan_lat_alloc = raw_cap;
+    }
+    me->fan_lat_cap = raw_cap;   // (<= fan_lat_alloc: nranks blocks at this cap's stride fit the allocation)
+    me->fan_lat_on = false;
+    TRY(fan_lat_clear(ctx, *me));
+    me->fan_lat_on = true;
+    return MPX_OK;
+}
+
+int mpx_fan_lat_disable(mpx_ctx* ctx, int rank) {
+    Rank* me = nullptr;
+    TRY(fan_lat_rank(ctx, rank, &me));
+    me->fan_lat_on = false;   // the blocks stay until finalize (no hipFree between calls)
+    return MPX_OK;
+}
+
+int mpx_fan_lat_reset(mpx_ctx* ctx, int rank) {
+    Rank* me = nullptr;
+    TRY(fan_lat_rank(ctx, rank, &me));
+    if (!me->fan_lat_on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    return fan_lat_clear(ctx, *me);
+}
+
+int mpx_fan_lat_get(mpx_ctx* ctx, int rank, int peer, mpx_lat* out) {
+    Rank* me = nullptr;
+    TRY(fan_lat_rank(ctx, rank, &me));
+    if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
+    TRY(fan_lat_peer(ctx, rank, peer));
+    if (!me->fan_lat_on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    LatBlock h{};
+    TRY(fan_lat_header(*me, peer, &h));
+    memset(out, 0, sizeof *out);
+    out->count = h.count;
+    out->calls = h.calls;
+    out->min_ticks = h.min_ticks;
+    out->max_ticks = h.max_ticks;
+    out->sum_ticks = h.sum_ticks;
+    out->max_iter = h.max_iter;
+    out->last_iters = h.last_iters;
+    out->tick_s = 1e-8;   // s_memrealtime: 100 MHz
+    memcpy(out->hist, h.hist, sizeof h.hist);
+    return MPX_OK;
+}
+
+int mpx_fan_lat_raw(mpx_ctx* ctx, int rank, int peer, uint64_t* stamps, int cap, int* n) {
+    Rank* me = nullptr;
+    TRY(fan_lat_rank(ctx, rank, &me));
+    if (!n || cap < 0 || (!stamps && cap > 0)) return fail(MPX_ERR_INVALID, "bad argument");
+    *n = 0;
+    TRY(fan_lat_peer(ctx, rank, peer));
+    if (!me->fan_lat_on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
+    DeviceGuard g(me->dev);
+    HIPCK(g.err);
+    LatBlock h{};
+    TRY(fan_lat_header(*me, peer, &h));
+    // t[0] alone says nothing: with raw_cap = 0 no stamp is reported
+    u64 have = me->fan_lat_cap > 0 ? h.raw_n : 0;
+    if (have > (u64)me->fan_lat_cap + 1) have = (u64)me->fan_lat_cap + 1;
+    if (have > (u64)cap) have = (u64)cap;
+    if (have) {
+        HIPCK(hipMemcpyAsync(stamps, fan_lat_block(*me, peer)->raw, (size_t)have * sizeof(u64), hipMemcpyDeviceToHost,
+                             me->stream));
         HIPCK(hipStreamSynchronize(me->stream));
     }
     *n = (int)have;

@@ -30,6 +30,7 @@ void mpxh_defaults(mpxh_options *o)
     o->timeout_ms = 10000;
     o->arm = 1;
     o->lat_cap = -1;
+    o->fan_lat_cap = -1;
 }
 
 int mpxh_engine_from_name(const char *s)
@@ -70,7 +71,8 @@ void mpxh_print_usage(FILE *f)
 		    -A <launch each run's kernel before the barrier 0|1 (default 1)>\n\
 		    -L <raw-cap: record every iteration's latency, lat-*.csv (kernel engine, not -x 1)>\n\
 		    -m <1: every run is one fan exchange, each rank with all others at once (kernel engine)>\n\
-		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n");
+		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n\
+		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -79,7 +81,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -118,6 +120,13 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
             const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > (1 << 22)) return MPXH_PARSE_BAD_VALUE; /* MPX_LAT_RAW_MAX */
             o->lat_cap = (int)v;
+            break;
+        }
+        case 'P': {
+            char *end = NULL;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > MPXH_FAN_LAT_RAW_MAX) return MPXH_PARSE_BAD_VALUE;
+            o->fan_lat_cap = (int)v;
             break;
         }
         default: return MPXH_PARSE_USAGE; /* includes -h and a missing value */
@@ -195,6 +204,11 @@ static int validate_fan(const mpxh_options *o, int world, FILE *err)
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
     if (o->fan && validate_fan(o, world, err)) return 1;
+    if (o->fan_lat_cap >= 0 && o->fan != 2) {
+        fprintf(err, "invalid -P %d without -m 2: per-link latencies are recorded by the lock-step LL fan exchange only\n",
+                o->fan_lat_cap);
+        return 1;
+    }
     if (o->lat_cap >= 0 && (o->nonblocking || o->engine != 0)) {
         fprintf(err, "invalid -L %d with %s: per-iteration latencies are recorded by the kernel engine's "
                      "ping-pong and unidir loops only\n",

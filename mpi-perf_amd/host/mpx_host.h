@@ -51,6 +51,10 @@ typedef struct mpxh_options {
                                            (mpx_xfer_fan); 2 = the same as a
                                            lock-step LL exchange (MPX_FAN_LL) */
     int arm_set;                    /* -A was given on the command line       */
+    int fan_lat_cap;                /* -P  raw_cap: with -m 2, record every
+                                           link's per-iteration exchange latency
+                                           (mpx_fan_lat_*), lat-*.csv; -1
+                                           (default) = off                    */
 } mpxh_options;
 
 /* parse status */
@@ -65,7 +69,7 @@ enum {
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:m:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:P:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -89,7 +93,7 @@ int mpxh_fan_peers(int world, int rank, int *peers);
 /* validate -L against -x / -e (the recorder traces the kernel engine's
    blocking loops only) and -m 1 against -a 1, an explicit -A 1, -L, -e, -d 1
    and a -b too large for world blocks (-m 2: the same, and a -b above
-   MPXH_FAN_LL_MAX); then group_size, mpi_perf.c:399-403.
+   MPXH_FAN_LL_MAX), and -P without -m 2; then group_size, mpi_perf.c:399-403.
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides
    by zero here (ppn == 0 in bidirectional mode): the caller raises SIGFPE. */
@@ -121,7 +125,10 @@ int mpxh_parse_gpu_list(const char *s, int *devs, int n);
 
 /* time strings, getformatted_time mpi_perf.c:341-353 */
 void mpxh_format_time(char *buf, size_t cap, int for_kusto);
-/* lat-*.csv (-L): header, and one line per recorded run; times in us */
+/* lat-*.csv (-L): header, and one line per recorded run; times in us
+   (-m 2 -P: one line per link and recorded run, Mode = 10) */
+#define MPXH_FAN_LAT_RAW_MAX (1 << 16) /* MPX_FAN_LAT_RAW_MAX, include/mpx_fan_lat.h */
+#define MPXH_FAN_LAT_MODE 10           /* the LL fan call's protocol number  */
 #define MPXH_LAT_HEADER                                                                                   \
     "Timestamp,JobId,Rank,PeerRank,Mode,BufferSize,NumOfBuffers,RunId,Count,MinUs,P50Us,P90Us,P99Us,P999Us," \
     "MaxUs,MeanUs,MaxIter\n"

@@ -243,10 +243,10 @@ static void open_logs(int rank, rank_files *f)
         fprintf(f->gpu_fp, "Timestamp,JobId,Rank,Engine,Mode,Device,PeerRank,PeerDevice,BufferSize,NumOfBuffers,"
                            "WallTimems,DeviceTimems,GBps,Protocol,Workgroups,CheckedPayloads,CheckFailures,RunId,RecvDone,"
                            "RecvDigest,Launch,Rccl\n");
-    /* -L: the latency side file, opened and rotated with the GPU side file
+    /* -L, -m 2 -P: the latency side file, opened and rotated with the GPU side file
        (a name of its own: neither "tcp*" nor "gpu-*.csv" matches it) */
     f->lat_fp = NULL;
-    if (opt.lat_cap >= 0) {
+    if (opt.lat_cap >= 0 || opt.fan_lat_cap >= 0) {
         snprintf(name, sizeof name, "%s/lat-%s-%d-%s.csv", opt.logfolder, opt.uuid, rank, ft);
         f->lat_fp = fopen(name, "w");
         if (f->lat_fp) fputs(MPXH_LAT_HEADER, f->lat_fp);
@@ -272,6 +272,24 @@ static int xfer_mode(void)
 {
     if (opt.uni_dir) return MPX_MODE_UNIDIR;
     return opt.nonblocking ? MPX_MODE_NONBLOCKING : MPX_MODE_PINGPONG;
+}
+
+/* one lat-*.csv line: a recorded run's distribution (-L: the rank's; -m 2 -P:
+   one link's, mode = MPXH_FAN_LAT_MODE) */
+static void write_lat_line(FILE *fp, const mpx_lat *l, const char *ts, int r, int peer, int mode, int B, long long run_idx)
+{
+    char line[1024];
+    const double us_tick = l->tick_s * 1e6;
+    const double us[7] = {(double)l->min_ticks * us_tick,
+                          (double)mpx_lat_quantile(l, 0.5) * us_tick,
+                          (double)mpx_lat_quantile(l, 0.9) * us_tick,
+                          (double)mpx_lat_quantile(l, 0.99) * us_tick,
+                          (double)mpx_lat_quantile(l, 0.999) * us_tick,
+                          (double)l->max_ticks * us_tick,
+                          l->count ? (double)l->sum_ticks * us_tick / (double)l->count : 0.0};
+    mpxh_format_lat(line, sizeof line, ts, opt.uuid, r, peer, mode, B, opt.iters, run_idx, (unsigned long long)l->count, us,
+                    (unsigned long long)l->max_iter);
+    fputs(line, fp);
 }
 
 /* the run loop of one rank, mpi_perf.c:470-569 */
@@ -371,17 +389,7 @@ static void *rank_main(void *arg)
                 if (lat && files.lat_fp) {
                     mpx_lat l;
                     MPX_CHECK(mpx_lat_get(ctx, r, &l));
-                    const double us_tick = l.tick_s * 1e6;
-                    const double us[7] = {(double)l.min_ticks * us_tick,
-                                          (double)mpx_lat_quantile(&l, 0.5) * us_tick,
-                                          (double)mpx_lat_quantile(&l, 0.9) * us_tick,
-                                          (double)mpx_lat_quantile(&l, 0.99) * us_tick,
-                                          (double)mpx_lat_quantile(&l, 0.999) * us_tick,
-                                          (double)l.max_ticks * us_tick,
-                                          l.count ? (double)l.sum_ticks * us_tick / (double)l.count : 0.0};
-                    mpxh_format_lat(line, sizeof line, ts, opt.uuid, r, peer, xfer_mode(), B, opt.iters, run_idx,
-                                    (unsigned long long)l.count, us, (unsigned long long)l.max_iter);
-                    fputs(line, files.lat_fp);
+                    write_lat_line(files.lat_fp, &l, ts, r, peer, xfer_mode(), B, run_idx);
                 }
             }
 
@@ -444,6 +452,8 @@ static void *rank_main_fan(void *arg)
     rank_files files = {NULL, NULL, wtime(), NULL};
     int peers[MPXH_MAX_RANKS];
     const int np = mpxh_fan_peers(world, r, peers);
+    const int lat = opt.fan_lat_cap >= 0; /* -P: every link's per-iteration latency (validated: -m 2) */
+    if (lat) MPX_CHECK(mpx_fan_lat_enable(ctx, r, opt.fan_lat_cap));
     for (int si = 0; si < nsizes; ++si) {
         const int B = sizes[si];
         const size_t stride = mpxh_fan_stride(B);
@@ -473,6 +483,7 @@ static void *rank_main_fan(void *arg)
                 fo.check = 1;
                 fo.expect_checksum = expect;
             }
+            if (lat) MPX_CHECK(mpx_fan_lat_reset(ctx, r)); /* each run's distribution is its own */
             start_barrier(); /* MPI_Barrier, mpi_perf.c:499 */
             const double t_start = wtime();
             mpx_timing tm;
@@ -497,6 +508,11 @@ static void *rank_main_fan(void *arg)
                             tm.protocol == 10 ? "fan_ll" : "fan", l->nwg,
                             (unsigned long long)(opt.check ? opt.iters : 0), l->check_failures, run_idx,
                             (unsigned long long)l->recv_done, (unsigned long long)l->recv_digest, "inline", "");
+                }
+                for (int k = 0; lat && files.lat_fp && k < np; ++k) {
+                    mpx_lat l;
+                    MPX_CHECK(mpx_fan_lat_get(ctx, r, peers[k], &l));
+                    write_lat_line(files.lat_fp, &l, ts, r, peers[k], MPXH_FAN_LAT_MODE, B, run_idx);
                 }
             }
 
@@ -523,6 +539,7 @@ static void *rank_main_fan(void *arg)
     }
     if (files.log_fp) fclose(files.log_fp);
     if (files.gpu_fp) fclose(files.gpu_fp);
+    if (files.lat_fp) fclose(files.lat_fp);
     return NULL;
 }
 
@@ -665,7 +682,7 @@ int main(int argc, char **argv)
     }
     if (pst == MPXH_PARSE_BAD_VALUE) {
         if (is_root()) {
-            fprintf(stderr, "bad value for -e / -S / -L\n");
+            fprintf(stderr, "bad value for -e / -S / -L / -P\n");
             mpxh_print_usage(stderr);
         }
         mpx_abort();

@@ -112,6 +112,7 @@ class Phases(C.Structure):
 
 LAT_BUCKETS = 464
 LAT_RAW_MAX = 1 << 22
+FAN_LAT_RAW_MAX = 1 << 16   # MPX_FAN_LAT_RAW_MAX: the link recorder's (fan_lat_enable)
 
 
 class Lat(C.Structure):
@@ -208,6 +209,11 @@ _SIGS = {
     "mpx_lat_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "mpx_lat_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Lat)]),
     "mpx_lat_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
+    "mpx_fan_lat_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mpx_fan_lat_disable": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_fan_lat_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_fan_lat_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Lat)]),
+    "mpx_fan_lat_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mpx_rccl_get_unique_id": (C.c_int, [C.c_void_p]),
     "mpx_rccl_init_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -306,6 +312,7 @@ class Context:
         self.nranks = nranks
         self.engine = engine
         self._lat_cap = {}   # rank -> raw_cap of its latency recorder (lat_enable)
+        self._fan_lat_cap = {}   # rank -> raw_cap of its link recorder (fan_lat_enable)
 
     def close(self) -> None:
         if self.h:
@@ -476,6 +483,36 @@ class Context:
         n = C.c_int(0)
         buf = (C.c_uint64 * max(cap, 1))()
         check(self.L.mpx_lat_raw(self.h, rank, buf, cap, C.byref(n)), "mpx_lat_raw")
+        return list(buf[:n.value])
+
+    # per-link latency recorder of the lock-step LL fan exchange (kernel engine)
+    def fan_lat_enable(self, rank: int, raw_cap: int = 0) -> None:
+        """mpx_fan_lat_enable: trace every link of rank's MPX_FAN_LL calls from
+        now on, keeping the first raw_cap iterations' stamps per link; resets"""
+        check(self.L.mpx_fan_lat_enable(self.h, rank, raw_cap), "mpx_fan_lat_enable")
+        self._fan_lat_cap[rank] = raw_cap
+
+    def fan_lat_disable(self, rank: int) -> None:
+        check(self.L.mpx_fan_lat_disable(self.h, rank), "mpx_fan_lat_disable")
+
+    def fan_lat_reset(self, rank: int) -> None:
+        check(self.L.mpx_fan_lat_reset(self.h, rank), "mpx_fan_lat_reset")
+
+    def fan_lat_get(self, rank: int, peer: int) -> dict:
+        """mpx_fan_lat_get: link (rank, peer)'s distribution since enable /
+        reset (the dict of lat_get; blocks are keyed by the peer's rank)"""
+        l = Lat()
+        check(self.L.mpx_fan_lat_get(self.h, rank, peer, C.byref(l)), "mpx_fan_lat_get")
+        return l.as_dict()
+
+    def fan_lat_raw(self, rank: int, peer: int, cap: int | None = None) -> list[int]:
+        """mpx_fan_lat_raw: link (rank, peer)'s stamps t[0 .. min(iters, raw_cap)]
+        of the last traced call that listed peer (cap: at most that many)"""
+        if cap is None:
+            cap = self._fan_lat_cap.get(rank, 0) + 1
+        n = C.c_int(0)
+        buf = (C.c_uint64 * max(cap, 1))()
+        check(self.L.mpx_fan_lat_raw(self.h, rank, peer, buf, cap, C.byref(n)), "mpx_fan_lat_raw")
         return list(buf[:n.value])
 
     def rccl_init_all(self) -> None:

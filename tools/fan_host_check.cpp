@@ -159,6 +159,22 @@ static int check_host() {
     fresh(); o.use_dotnet = 1;           REQUIRE(mpxh_validate(&o, 3, sink) == 1);
     fresh(); o.buff_sz = 0x7fffffff;     REQUIRE(mpxh_validate(&o, 3, sink) == 1);
     fresh(); o.sweep_min = 1; o.sweep_max = 1 << 30; REQUIRE(mpxh_validate(&o, 3, sink) == 1);
+    // -P (the link recorder) goes with -m 2 only
+    fresh(); o.fan_lat_cap = 64;                            REQUIRE(mpxh_validate(&o, 3, sink) == 1);
+    fresh(); o.fan = 2; o.buff_sz = 4096; o.fan_lat_cap = 64; REQUIRE(mpxh_validate(&o, 3, sink) == 0);
+    fresh(); o.fan = 0; o.fan_lat_cap = 0;                  REQUIRE(mpxh_validate(&o, 2, sink) == 1);
+    fresh(); o.fan = 2; o.buff_sz = 8; o.fan_lat_cap = 0; o.lat_cap = 0; REQUIRE(mpxh_validate(&o, 3, sink) == 1);
+    {
+        const char* argv[] = {"x", "-m", "2", "-P", "65536", nullptr};
+        mpxh_defaults(&o);
+        REQUIRE(o.fan_lat_cap == -1);
+        REQUIRE(mpxh_parse_args(&o, 5, const_cast<char**>(argv)) == MPXH_PARSE_OK && o.fan_lat_cap == 65536 && o.fan == 2);
+        for (const char* bad : {"-1", "x", "12x", "65537"}) {
+            const char* av[] = {"x", "-P", bad, nullptr};
+            mpxh_defaults(&o);
+            REQUIRE(mpxh_parse_args(&o, 3, const_cast<char**>(av)) == MPXH_PARSE_BAD_VALUE);
+        }
+    }
     fclose(sink);
     return 0;
 }

@@ -31,6 +31,18 @@ and, once per N, the 8-byte pair ping-pong's half round trip between ranks 0
 and 1.  Loopback figures as above: no link is in them, no pass mark.
 
     python tools/fan_probe.py --ll [--repeats 5] [--ranks 2,4,8] > profiles/fan_ll_loopback.jsonl
+
+--ll --lat: the link recorder (mpx_fan_lat_*) on the same calls.  Per N and per
+block of 8 B and 4 KiB, one JSON line with
+
+    slowest / fastest link   (by mean) p50, p99 and max of its per-iteration
+                             exchange latency, from one traced call
+    observer cost            traced minus untraced time per iteration (the
+                             slowest link's device_s / iters as above), the
+                             same calls in the same process, alternating
+                             untraced / traced, best of `--repeats` each
+
+    python tools/fan_probe.py --ll --lat [--repeats 5] [--ranks 2,4,8] > profiles/fan_ll_lat_loopback.jsonl
 """
 import argparse
 import json
@@ -44,7 +56,10 @@ ap.add_argument("--iters", type=int, default=50)
 ap.add_argument("--bytes", type=int, default=4 << 20)
 ap.add_argument("--ranks", default="2,4,8")
 ap.add_argument("--ll", action="store_true")
+ap.add_argument("--lat", action="store_true")
 args = ap.parse_args()
+if args.lat and not args.ll:
+    ap.error("--lat goes with --ll")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-perf_amd"))
 import mpx  # noqa: E402
 from mpx.schedule import all_pairs_rounds  # noqa: E402
@@ -76,6 +91,7 @@ def together(n, fn):
 
 
 LL_BLOCKS = (8, 256, 2048, 4096)
+LAT_BLOCKS = (8, 4096)
 LL_CALL_S = 0.010
 
 
@@ -120,6 +136,42 @@ def ll_probe(n):
                     break
                 iters = int(min(200000, max(iters, LL_CALL_S / max(2 * t, 1e-9) * 1.2)))
             return min(once(iters) for _ in range(args.repeats)), iters
+
+        def ll_call(b):
+            return lambda r, it: c.fan(r, peers[r], it, bufs[r][0], bufs[r][1], b, stride, timeout_ms=20000, ll=True)
+
+        def link_us(lat):
+            us = lat["tick_s"] * 1e6
+            return dict(p50_us=round(mpx.lat_quantile(lat, 0.5) * us, 3), p99_us=round(mpx.lat_quantile(lat, 0.99) * us, 3),
+                        max_us=round(lat["max_ticks"] * us, 3), mean_us=round(lat["sum_ticks"] * us / lat["count"], 3),
+                        max_iter=lat["max_iter"])
+
+        if args.lat:
+            for b in LAT_BLOCKS:
+                _, iters = best(ll_call(b))                            # (recorder off: the call length)
+                un, tr = [], []
+                for _ in range(args.repeats):                          # alternating: untraced, traced
+                    for r in range(n):
+                        c.fan_lat_disable(r)
+                    un.append(per_iter(ll_call(b), iters))
+                    for r in range(n):
+                        c.fan_lat_enable(r, 0)                         # (resets)
+                    tr.append(per_iter(ll_call(b), iters))
+                # the distribution: the last traced call's, every link's
+                lats = {(r, p): c.fan_lat_get(r, p) for r in range(n) for p in peers[r]}
+                by_mean = sorted(lats, key=lambda k: lats[k]["sum_ticks"] / lats[k]["count"])
+                for r in range(n):
+                    c.fan_lat_disable(r)
+                print(json.dumps(dict(
+                    kind="loopback (one GPU, no link in it; no pass mark, no headline)", ranks=n, links_per_rank=n - 1,
+                    block_bytes=b, repeats=args.repeats, iters=iters,
+                    untraced_us_per_iter=round(min(un) * 1e6, 4), traced_us_per_iter=round(min(tr) * 1e6, 4),
+                    observer_cost_us_per_iter=round((min(tr) - min(un)) * 1e6, 4),
+                    untraced_range_us=[round(min(un) * 1e6, 4), round(max(un) * 1e6, 4)],
+                    traced_range_us=[round(min(tr) * 1e6, 4), round(max(tr) * 1e6, 4)],
+                    slowest_link=dict(rank=by_mean[-1][0], peer=by_mean[-1][1], **link_us(lats[by_mean[-1]])),
+                    fastest_link=dict(rank=by_mean[0][0], peer=by_mean[0][1], **link_us(lats[by_mean[0]])))), flush=True)
+            return
 
         half, half_iters = pair_half_rtt()
         for b in LL_BLOCKS:
