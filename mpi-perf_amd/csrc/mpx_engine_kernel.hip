@@ -204,7 +204,7 @@ int prepare_call(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank,
     if (const char* v = getenv("MPX_LL_MAX")) a.ll_max = atoi(v) < kLLMaxBytes ? atoi(v) : kLLMaxBytes;
     a.cnt = me.cnt;
     // the latency recorder traces the blocking loops only (launch_xfer)
-    a.lat = (me.lat_on && mode != MPX_MODE_NONBLOCKING) ? me.lat : nullptr;
+    a.lat = (me.lat.on && mode != MPX_MODE_NONBLOCKING) ? me.lat.block(0) : nullptr;
     const TestKnobs knobs = test_knobs();
     a.skip_push = knobs.skip_push;
     a.no_pull_wait = knobs.no_pull_wait ? 1 : 0;
@@ -662,8 +662,8 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
             la.lag_ticks = (u64)knobs.lag_us * 100ull;   // s_memrealtime: 100 MHz
         }
         // the link recorder (mpx_fan_lat_enable): launch_fan_ll then picks the traced kernels
-        la.lat = me.fan_lat_on ? me.fan_lat : nullptr;
-        la.lat_stride = lat_block_bytes(me.fan_lat_cap);
+        la.lat = me.fan_lat.on ? me.fan_lat.base : nullptr;
+        la.lat_stride = me.fan_lat.stride();
     }
     const int lst = launch_call(me, c, [&] { return ll ? launch_fan_ll(la, me.stream) : launch_fan(a, grid, me.stream); });
     if (lst != MPX_OK) {

@@ -152,7 +152,7 @@ __host__ __device__ inline int ring_slot(int j, int iters, int slots) { return (
 // itself: the kernel bounds its raw stores by the very word the allocation
 // was sized with.  The link recorder (mpx_fan_lat_enable) is nranks such
 // blocks, one per peer rank, each written by lane 0 of that link's workgroup
-// of the rank's traced LL fan calls (k_xfer_fan_ll_lat; FanLLArgs.lat).
+// of the rank's traced LL fan calls (k_xfer_fan_ll<., true>; FanLLArgs.lat).
 struct LatBlock {
     u64 count, calls, min_ticks, max_ticks, sum_ticks, max_iter, last_iters;   // mpx_lat's, accumulated
     u64 raw_cap;            // iterations of a call whose end stamp is kept (host, at enable)

@@ -9,8 +9,8 @@
 //   k_xfer_fan  one rank's blocks to and from several peers in one launch
 //               (mpx_xfer_fan): every workgroup owns one chunk of one link
 //   k_xfer_fan_ll  the same with MPX_FAN_LL: per link a lock-step exchange of
-//               LL granules, one workgroup per link (k_xfer_fan_ll_lat: traced
-//               per link, mpx_fan_lat_*)
+//               LL granules, one workgroup per link (<CHECK, LAT>: LAT is the
+//               form traced per link, mpx_fan_lat_*)
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -1238,7 +1238,7 @@ __device__ __forceinline__ u64 lat_stamp() {
 }
 
 // ANYWG: lane 0 of EVERY workgroup traces, into a block of its workgroup's own
-// (k_xfer_fan_ll_lat: workgroup k is link k); false: workgroup 0's lane 0 only.
+// (k_xfer_fan_ll<., true>: workgroup k is link k); false: workgroup 0's lane 0 only.
 template <bool LAT, bool ANYWG = false>
 struct LatTrace {
     __device__ bool on() const { return false; }
@@ -1355,14 +1355,6 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
                 if (a.check) L.check(n, i);
                 L.send(n, ++txs, skip);                // Send(tx, B, tag 2)
             }
-            if constexpr (LAT) {                       // one clock read: the iteration's end, and
-                if (T.on()) {                          // for i = 0 also the kTsFirst stamp
-                    const u64 t = T.tick(i);
-                    if (i == 0) L.ts[kTsFirst] = t;
-                }
-            } else if (i == 0) {
-                L.stamp(kTsFirst);
-            }
         } else if constexpr (MODE == MPX_MODE_UNIDIR) {  // mpi_perf.c:132-144
             if constexpr (GROUP == 1) {
                 L.send(n, ++txs, skip);                // Send(tx, B)
@@ -1375,14 +1367,6 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
                 ++done;
                 if (a.check) { L.check(n, i); if (!L.grid_sync(i)) break; }
                 L.send(1, ++txs, skip);                // Send(tx, 1)
-            }
-            if constexpr (LAT) {                       // one clock read: the iteration's end, and
-                if (T.on()) {                          // for i = 0 also the kTsFirst stamp
-                    const u64 t = T.tick(i);
-                    if (i == 0) L.ts[kTsFirst] = t;
-                }
-            } else if (i == 0) {
-                L.stamp(kTsFirst);
             }
         } else {                                       // mpi_perf.c:95-124
             // Isend + Irecv, slot `inflight`.  A receiver waits only at the
@@ -1404,6 +1388,17 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
                 inflight = 0;
             } else {
                 ++inflight;
+            }
+        }
+        // the end of a blocking iteration (the breaks above leave the loop)
+        if constexpr (MODE != MPX_MODE_NONBLOCKING) {
+            if constexpr (LAT) {                       // one clock read: the iteration's end, and
+                if (T.on()) {                          // for i = 0 also the kTsFirst stamp
+                    const u64 t = T.tick(i);
+                    if (i == 0) L.ts[kTsFirst] = t;
+                }
+            } else if (i == 0) {
+                L.stamp(kTsFirst);
             }
         }
     }
@@ -1831,14 +1826,22 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
 // iteration iters / 2, where a single-buffered zone would break.
 // Every wait is bounded (should_stop / give_up); the call ends as k_xfer_fan's
 // does.  Resource figures: DESIGN.md "Fan exchange".
-// k_xfer_fan_ll_lat (below) is the traced form (mpx_fan_lat_*; LatTrace<true,
-// true>): lane 0 of EVERY workgroup is a tracer, into the block of its link's
-// peer (q.lat + peer * q.lat_stride).  t[0] is a clock read of the link's own
-// behind the posted wait (Loop::stamp records workgroup 0 only, for the Fin
-// line); t[i + 1] is read at the bottom of iteration i, behind wait_ll and
-// the check.  The fold (end) comes before the workgroup counts itself out.
+// LAT is the traced form (mpx_fan_lat_*; LatTrace<true, true>): lane 0 of
+// EVERY workgroup is a tracer, into the block of its link's peer (q.lat + peer
+// * q.lat_stride).  t[0] is a clock read of the link's own behind the posted
+// wait (Loop::stamp records workgroup 0 only, for the Fin line); t[i + 1] is
+// read at the bottom of iteration i, behind wait_ll and the check.  The fold
+// (end) comes before the workgroup counts itself out.
+// One kernel template, the traced lines under `if constexpr (LAT)`: a template
+// parameter on the kernel itself costs nothing — the LAT = false instantiations
+// are instruction for instruction the kernels that had no recorder, the LAT =
+// true ones the traced copy this replaced.  A `__device__` body shared between
+// kernels is NOT free: routing this loop, or the end-of-call code below, through
+// one changes the callers' register allocation (k_xfer_fan: 73 -> 75 VGPRs),
+// so the body stands here in the kernel, and k_xfer_fan keeps end-of-call code
+// of its own (DESIGN.md "Link recorder").
 // ---------------------------------------------------------------------------
-template <bool CHECK>
+template <bool CHECK, bool LAT>
 __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan_ll(FanLLArgs q) {
     __shared__ int s_abort;
     __shared__ u64 lds4[4];
@@ -1881,104 +1884,12 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
         ok = !L.aborted();
     }
     L.stamp(kTsPosted);
-    u64 done = 0;
-    for (int i = 0; ok && i < f.iters; ++i) {
-        const u64 s = tx0 + (u64)i + 1, r = rx0 + (u64)i + 1;
-        const unsigned out = (unsigned)(s & 1) * kFanLLHalf, in = (unsigned)(r & 1) * kFanLLHalf;
-        if (f.skip_push == i + 1) L.push_ll_tags_only(n, s, out);   // (test knob: this payload is "lost")
-        else L.push_ll(n, s, out);
-        if (q.lag_ticks && k == q.lag_link && i == f.iters / 2) {   // (test knob)
-            if (threadIdx.x == 0) {
-                const u64 t0 = now_ticks();
-                while (now_ticks() - t0 < q.lag_ticks) __builtin_amdgcn_s_sleep(127);
-            }
-            __syncthreads();
+    LatTrace<LAT, true> T;
+    if constexpr (LAT) {
+        if (T.on()) {   // t[0]: this link's own read, behind its own posted wait
+            const u64 t = lat_stamp();
+            T.begin(reinterpret_cast<LatBlock*>(q.lat + (u64)lk.peer * q.lat_stride), t, t, f.iters);
         }
-        ok = L.wait_ll(n, r, i, in);
-        if (!ok) break;
-        ++done;
-        if constexpr (CHECK) L.check(n, i);
-    }
-    L.stamp(kTsLoop);
-    // the end of the link and of the call, as in k_xfer_fan
-    drain_stores();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_min(&lk.recv_done, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_max(&lk.t_end, now_ticks(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (!L.last_to_finish()) return;
-    // workgroup 0, every other workgroup done: the call's receive count and
-    // digest (of a call that completed: a timeout fails it anyway)
-    u64 part = 0, dpart = 0;
-    for (int j = threadIdx.x; j < f.nlinks; j += kBlock)
-        part += __hip_atomic_load(&f.tab->link[j].recv_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (CHECK && !__hip_atomic_load(&f.gbar[kScrAbort], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        const u64 fmix = mix64((u64)n);
-        for (int j = threadIdx.x; j < f.nlinks * f.iters; j += kBlock)
-            dpart += __hip_atomic_load(&f.csum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ fmix;
-    }
-    const u64 d = block_sum(part, lds4);
-    const u64 g = block_sum(dpart, lds4);
-    if (threadIdx.x == 0) {
-        L.rdone = d;
-        L.rdig = g;
-    }
-    L.finish_last();
-}
-
-// k_xfer_fan_ll_lat: k_xfer_fan_ll with the link recorder (see above).  A copy
-// of its own, not a shared body: sharing one changed the untraced kernels'
-// register allocation, and those stay instruction for instruction what they
-// were (k_xfer_fan keeps its own end-of-call code for the same reason).  Keep
-// the two in step.
-template <bool CHECK>
-__global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan_ll_lat(FanLLArgs q) {
-    __shared__ int s_abort;
-    __shared__ u64 lds4[4];
-    if (threadIdx.x == 0) s_abort = 0;
-    const FanArgs& f = q.f;
-    const int k = (int)blockIdx.x;
-    FanLink& lk = f.tab->link[k];
-    const long long n = f.len;
-    XferArgs x{};   // the link as a pair: what Loop's LL, wait and end-of-call helpers read
-    x.tx = f.tx + lk.off;
-    x.rx = f.rx + lk.off;
-    x.my_mb = f.my_mb;
-    x.peer_mb = lk.peer_mb;
-    x.my_slot = f.my_slot;
-    x.peer_slot = lk.peer;
-    x.status = f.status;
-    x.gbar = f.gbar;
-    x.csum = f.csum + lk.csum0;
-    x.timeout_ticks = f.timeout_ticks;
-    x.done_token = f.done_token;
-    x.iters = f.iters;
-    x.ll_max = MPX_FAN_LL_MAX;
-    Loop<MPX_MODE_PINGPONG, true> L{x, &s_abort, lds4, nullptr, {}};
-    __syncthreads();
-    L.stamp(kTsEntry);
-    const u64 tx0 = lk.tx_seq0, rx0 = lk.rx_seq0;
-    if (threadIdx.x == 0) st_sys(&lk.peer_mb->posted[f.my_slot], lk.call);
-    L.preload_ll(n);
-    bool ok = f.iters > 0;
-    if (ok) {
-        if (threadIdx.x == 0) {
-            const u64 t0 = now_ticks();
-            u64 spins = 0;
-            while (ld_sys(&f.my_mb->posted[lk.peer]) < lk.call) {
-                if (L.should_stop(++spins, t0)) { L.give_up(0); break; }
-                __builtin_amdgcn_s_sleep(1);
-            }
-        }
-        __syncthreads();
-        ok = !L.aborted();
-    }
-    L.stamp(kTsPosted);
-    LatTrace<true, true> T;
-    if (T.on()) {   // t[0]: this link's own read, behind its own posted wait
-        const u64 t = lat_stamp();
-        T.begin(reinterpret_cast<LatBlock*>(q.lat + (u64)lk.peer * q.lat_stride), t, t, f.iters);
     }
     u64 done = 0;
     for (int i = 0; ok && i < f.iters; ++i) {
@@ -1997,10 +1908,12 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
         if (!ok) break;
         ++done;
         if constexpr (CHECK) L.check(n, i);
-        if (T.on()) T.tick(i);   // one clock read: the bottom of iteration i
+        if constexpr (LAT) {
+            if (T.on()) T.tick(i);   // one clock read: the bottom of iteration i
+        }
     }
     L.stamp(kTsLoop);
-    T.end();   // (before the drain: the fold's stores are out when the workgroup counts itself out)
+    if constexpr (LAT) T.end();   // (before the drain: the fold's stores are out when the workgroup counts itself out)
     // the end of the link and of the call, as in k_xfer_fan
     drain_stores();
     __syncthreads();
@@ -2098,8 +2011,8 @@ hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s) {
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
     // the link recorder on (a.lat): the traced instantiations
     if (a.lat && a.lat_stride < sizeof(LatBlock)) return hipErrorInvalidValue;
-    void (*k)(FanLLArgs) = a.lat ? (a.f.check ? k_xfer_fan_ll_lat<true> : k_xfer_fan_ll_lat<false>)
-                                 : (a.f.check ? k_xfer_fan_ll<true> : k_xfer_fan_ll<false>);
+    void (*k)(FanLLArgs) = a.lat ? (a.f.check ? k_xfer_fan_ll<true, true> : k_xfer_fan_ll<false, true>)
+                                 : (a.f.check ? k_xfer_fan_ll<true, false> : k_xfer_fan_ll<false, false>);
     hipLaunchKernelGGL(k, dim3((unsigned)a.f.nlinks), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }

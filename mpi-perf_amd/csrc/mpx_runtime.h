@@ -138,6 +138,20 @@ enum MailboxKind { kMbUncached = 0, kMbFine = 1, kMbCoarse = 2 };
 // SDMA chunk
 typedef std::tuple<int, int, int, long long, u64, int> SdmaKey;
 
+// A latency recorder's device memory (mpx_lat_*, mpx_fan_lat_*): `blocks`
+// LatBlocks, stride() apart.  The allocation holds `blocks` blocks of raw_cap
+// `alloc`; cap <= alloc is the raw_cap in force, so the blocks at its stride
+// fit the allocation.
+struct Recorder {
+    unsigned char* base = nullptr;
+    int blocks = 0;
+    int alloc = 0;                 // raw_cap the blocks were allocated for
+    int cap = 0;                   // raw_cap in force (the blocks' stride)
+    bool on = false;               // the rank's calls are traced
+    size_t stride() const { return lat_block_bytes(cap); }
+    LatBlock* block(int i) const { return reinterpret_cast<LatBlock*>(base + (size_t)i * stride()); }
+};
+
 struct Rank {
     bool local = false;
     bool imported = false;
@@ -165,15 +179,9 @@ struct Rank {
     unsigned char* ring = nullptr; // non-blocking check mode's receive slots 1..S-1
     uint64_t ring_bytes = 0;       //   (allocated on first use, or at export: ensure_ring)
     std::vector<void*> retired;    // outgrown csum arrays and recorder blocks (freed at finalize)
-    LatBlock* lat = nullptr;       // latency recorder (mpx_lat_enable), device memory
-    int lat_alloc = 0;             //   raw_cap the block was allocated for
-    int lat_cap = 0;               //   raw_cap in force
-    bool lat_on = false;           //   blocking calls of this rank are traced
-    unsigned char* fan_lat = nullptr;   // link recorder (mpx_fan_lat_enable): ctx->nranks LatBlocks in device
-                                   //   memory, lat_block_bytes(fan_lat_cap) apart, keyed by peer rank
-    int fan_lat_alloc = 0;         //   raw_cap the blocks were allocated for
-    int fan_lat_cap = 0;           //   raw_cap in force (the blocks' stride)
-    bool fan_lat_on = false;       //   MPX_FAN_LL calls of this rank are traced per link
+    Recorder lat;                  // latency recorder (mpx_lat_enable): one block; on: blocking calls are traced
+    Recorder fan_lat;              // link recorder (mpx_fan_lat_enable): ctx->nranks blocks, keyed by peer
+                                   //   rank; on: MPX_FAN_LL calls of this rank are traced per link
     FanTable* fan_tab = nullptr;   // fan exchange (mpx_xfer_fan): the link table in device memory
     FanTable* fan_host = nullptr;  //   and its pinned host image (allocated on the first fan call)
     u64 tx_seq[MPX_MAX_RANKS] = {};

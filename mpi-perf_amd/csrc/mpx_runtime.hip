@@ -132,6 +132,21 @@ int ensure_csum(Rank& rk, int iters) {
 
 namespace {
 
+// Frees a local rank's device and host memory (rk.dev current, its stream
+// drained): mpx_finalize, and release_rank on a failed attach.
+void free_rank_memory(Rank& rk) {
+    if (rk.mb) (void)hipFree(rk.mb);
+    if (rk.ring) (void)hipFree(rk.ring);
+    if (rk.scratch) (void)hipFree(rk.scratch);
+    if (rk.csum) (void)hipFree(rk.csum);
+    if (rk.lat.base) (void)hipFree(rk.lat.base);
+    if (rk.fan_lat.base) (void)hipFree(rk.fan_lat.base);
+    if (rk.fan_tab) (void)hipFree(rk.fan_tab);
+    if (rk.fan_host) (void)hipHostFree(rk.fan_host);
+    for (void* q : rk.retired) (void)hipFree(q);
+    if (rk.status) (void)hipHostFree(rk.status);
+}
+
 // Bytes of a rank's check-mode receive ring: up to 255 further slots of the
 // attached length, capped at MPX_CHECK_RING_BYTES (default 64 MiB; 0 = rx
 // only, one slot per link).
@@ -589,16 +604,7 @@ int mpx_finalize(mpx_ctx* ctx) {
         Rank& rk = ctx->r[i];
         if (!rk.local) continue;
         DeviceGuard g(rk.dev);
-        if (rk.mb) (void)hipFree(rk.mb);
-        if (rk.ring) (void)hipFree(rk.ring);
-        if (rk.scratch) (void)hipFree(rk.scratch);
-        if (rk.csum) (void)hipFree(rk.csum);
-        if (rk.lat) (void)hipFree(rk.lat);
-        if (rk.fan_lat) (void)hipFree(rk.fan_lat);
-        if (rk.fan_tab) (void)hipFree(rk.fan_tab);
-        if (rk.fan_host) (void)hipHostFree(rk.fan_host);
-        for (void* q : rk.retired) (void)hipFree(q);
-        if (rk.status) (void)hipHostFree(rk.status);
+        free_rank_memory(rk);
     }
     for (auto& kv : ctx->allocs) {
         DeviceGuard g(kv.second.dev);
@@ -833,16 +839,7 @@ int attach_resources(Rank& rk) {
 // create_rank_stream: free, never destroy).
 void release_rank(Rank& rk) {
     if (rk.stream) (void)hipStreamSynchronize(rk.stream);
-    if (rk.mb) (void)hipFree(rk.mb);
-    if (rk.ring) (void)hipFree(rk.ring);
-    if (rk.scratch) (void)hipFree(rk.scratch);
-    if (rk.csum) (void)hipFree(rk.csum);
-    if (rk.lat) (void)hipFree(rk.lat);
-    if (rk.fan_lat) (void)hipFree(rk.fan_lat);
-    if (rk.fan_tab) (void)hipFree(rk.fan_tab);
-    if (rk.fan_host) (void)hipHostFree(rk.fan_host);
-    for (void* q : rk.retired) (void)hipFree(q);
-    if (rk.status) (void)hipHostFree(rk.status);
+    free_rank_memory(rk);
     rk.ev0.reset();
     rk.ev1.reset();
     if (rk.stream) release_rank_stream(rk.dev, rk.stream);
@@ -1215,91 +1212,84 @@ int mpx_last_phases(mpx_ctx* ctx, int rank, mpx_phases* out) {
     return MPX_OK;
 }
 
-// ---- per-iteration latency recorder (include/mpx.h) -------------------------
+// ---- latency recorders (include/mpx.h, include/mpx_fan_lat.h) ---------------
+// mpx_lat_*: one block per rank, written by the blocking pair loops.
+// mpx_fan_lat_*: ctx->nranks blocks per rank, keyed by peer rank, written by
+// the LL fan exchange's links.  One set of helpers over Recorder; every entry
+// point keeps its own argument checks, status codes and messages.
 namespace {
-// The rank a recorder call names: local, and holding no armed call — an armed
-// kernel is already running on the rank's stream, which every recorder call
-// uses (and has read its recorder pointer).
-int lat_rank(mpx_ctx* ctx, int rank, Rank** out) {
+// The rank a recorder call names: local (else `not_local`), and holding no
+// armed call — an armed kernel is already running on the rank's stream, which
+// every recorder call uses (and has read its recorder pointer).
+int rec_rank(mpx_ctx* ctx, int rank, int not_local, Rank** out) {
     if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
-    if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) return fail(MPX_ERR_STATE, "rank %d is not a local rank", rank);
+    if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) return fail(not_local, "rank %d is not a local rank", rank);
     if (ctx->r[rank].armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", rank);
     *out = &ctx->r[rank];
     return MPX_OK;
 }
-// Statistics, histogram and raw count back to zero, raw_cap in force; on the
-// rank's stream, so the rank's next kernel starts behind it.
-int lat_clear(Rank& me) {
+int lat_rank(mpx_ctx* ctx, int rank, Rank** out) { return rec_rank(ctx, rank, MPX_ERR_STATE, out); }
+int fan_lat_rank(mpx_ctx* ctx, int rank, Rank** out) { return rec_rank(ctx, rank, MPX_ERR_INVALID, out); }
+int fan_lat_peer(const mpx_ctx* ctx, int rank, int peer) {
+    if (peer < 0 || peer >= ctx->nranks || peer == rank) return fail(MPX_ERR_INVALID, "rank %d: peer rank %d", rank, peer);
+    return MPX_OK;
+}
+// Every block: statistics, histogram and raw count back to zero, raw_cap in
+// force; on the rank's stream, so the rank's next kernel starts behind it.
+int rec_clear(Rank& me, const Recorder& rc) {
     LatBlock h{};
-    h.raw_cap = (u64)me.lat_cap;
-    HIPCK(hipMemcpyAsync(me.lat, &h, offsetof(LatBlock, raw), hipMemcpyHostToDevice, me.stream));
+    h.raw_cap = (u64)rc.cap;
+    for (int i = 0; i < rc.blocks; ++i)
+        HIPCK(hipMemcpyAsync(rc.block(i), &h, offsetof(LatBlock, raw), hipMemcpyHostToDevice, me.stream));
     HIPCK(hipStreamSynchronize(me.stream));
     return MPX_OK;
 }
-int lat_header(Rank& me, LatBlock* h) {
+int rec_header(Rank& me, const Recorder& rc, int i, LatBlock* h) {
     // the rank's own stream: behind the rank's last kernel (an armed call's
     // completion word comes before its kernel retires), and no wait for
     // other ranks' kernels (finish_xfer)
-    HIPCK(hipMemcpyAsync(h, me.lat, offsetof(LatBlock, raw), hipMemcpyDeviceToHost, me.stream));
+    HIPCK(hipMemcpyAsync(h, rc.block(i), offsetof(LatBlock, raw), hipMemcpyDeviceToHost, me.stream));
     HIPCK(hipStreamSynchronize(me.stream));
     return MPX_OK;
 }
-}  // namespace
-
-int mpx_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
-    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
-    if (ctx->engine != MPX_ENGINE_KERNEL)
-        return fail(MPX_ERR_UNSUPPORTED, "the latency recorder runs inside the kernel engine's loop: not this engine");
-    Rank* me = nullptr;
-    TRY(lat_rank(ctx, rank, &me));
-    if (raw_cap < 0 || raw_cap > MPX_LAT_RAW_MAX) return fail(MPX_ERR_INVALID, "raw_cap %d not in [0,%d]", raw_cap, MPX_LAT_RAW_MAX);
-    DeviceGuard g(me->dev);
+// Allocates (or regrows, for a larger raw_cap) `blocks` blocks, puts raw_cap in
+// force, clears them and turns the recorder on.  A smaller raw_cap keeps the
+// allocation: `blocks` blocks at the smaller stride fit it.
+int rec_enable(Rank& me, Recorder& rc, int blocks, int raw_cap, int cap_max, const char* what) {
+    if (raw_cap < 0 || raw_cap > cap_max) return fail(MPX_ERR_INVALID, "raw_cap %d not in [0,%d]", raw_cap, cap_max);
+    DeviceGuard g(me.dev);
     HIPCK(g.err);
-    if (!me->lat || me->lat_alloc < raw_cap) {
+    if (!rc.base || rc.alloc < raw_cap) {
         // (no hipFree here: it waits for the whole device, ensure_csum)
+        const size_t bytes = (size_t)blocks * lat_block_bytes(raw_cap);
         void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, lat_block_bytes(raw_cap));
+        const hipError_t e = hipMalloc(&p, bytes);
         if (e == hipErrorOutOfMemory) {
             (void)hipGetLastError();
-            return fail(MPX_ERR_NOMEM, "latency recorder of %zu B on device %d", lat_block_bytes(raw_cap), me->dev);
+            return fail(MPX_ERR_NOMEM, "%s of %zu B on device %d", what, bytes, me.dev);
         }
         HIPCK(e);
-        if (me->lat) me->retired.push_back(me->lat);
-        me->lat = static_cast<LatBlock*>(p);
-        me->lat_alloc = raw_cap;
+        if (rc.base) me.retired.push_back(rc.base);
+        rc.base = static_cast<unsigned char*>(p);
+        rc.blocks = blocks;
+        rc.alloc = raw_cap;
     }
-    me->lat_cap = raw_cap;
-    me->lat_on = false;
-    TRY(lat_clear(*me));
-    me->lat_on = true;
+    rc.cap = raw_cap;
+    rc.on = false;
+    TRY(rec_clear(me, rc));
+    rc.on = true;
     return MPX_OK;
 }
-
-int mpx_lat_disable(mpx_ctx* ctx, int rank) {
-    Rank* me = nullptr;
-    TRY(lat_rank(ctx, rank, &me));
-    me->lat_on = false;   // the block stays until finalize (no hipFree between calls)
-    return MPX_OK;
-}
-
-int mpx_lat_reset(mpx_ctx* ctx, int rank) {
-    Rank* me = nullptr;
-    TRY(lat_rank(ctx, rank, &me));
-    if (!me->lat_on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
-    DeviceGuard g(me->dev);
+int rec_reset(Rank& me, const Recorder& rc) {
+    DeviceGuard g(me.dev);
     HIPCK(g.err);
-    return lat_clear(*me);
+    return rec_clear(me, rc);
 }
-
-int mpx_lat_get(mpx_ctx* ctx, int rank, mpx_lat* out) {
-    Rank* me = nullptr;
-    TRY(lat_rank(ctx, rank, &me));
-    if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
-    if (!me->lat_on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
-    DeviceGuard g(me->dev);
+int rec_get(Rank& me, const Recorder& rc, int i, mpx_lat* out) {
+    DeviceGuard g(me.dev);
     HIPCK(g.err);
     LatBlock h{};
-    TRY(lat_header(*me, &h));
+    TRY(rec_header(me, rc, i, &h));
     memset(out, 0, sizeof *out);
     out->count = h.count;
     out->calls = h.calls;
@@ -1313,64 +1303,64 @@ int mpx_lat_get(mpx_ctx* ctx, int rank, mpx_lat* out) {
     memcpy(out->hist, h.hist, sizeof h.hist);
     return MPX_OK;
 }
+// The last traced call's stamps of block i: at most cap, raw_cap + 1 and raw_n.
+int rec_raw(Rank& me, const Recorder& rc, int i, uint64_t* stamps, int cap, int* n) {
+    DeviceGuard g(me.dev);
+    HIPCK(g.err);
+    LatBlock h{};
+    TRY(rec_header(me, rc, i, &h));
+    // t[0] alone says nothing: with raw_cap = 0 no stamp is reported
+    u64 have = rc.cap > 0 ? h.raw_n : 0;
+    if (have > (u64)rc.cap + 1) have = (u64)rc.cap + 1;
+    if (have > (u64)cap) have = (u64)cap;
+    if (have) {
+        HIPCK(hipMemcpyAsync(stamps, rc.block(i)->raw, (size_t)have * sizeof(u64), hipMemcpyDeviceToHost, me.stream));
+        HIPCK(hipStreamSynchronize(me.stream));
+    }
+    *n = (int)have;
+    return MPX_OK;
+}
+}  // namespace
+
+int mpx_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
+    if (ctx->engine != MPX_ENGINE_KERNEL)
+        return fail(MPX_ERR_UNSUPPORTED, "the latency recorder runs inside the kernel engine's loop: not this engine");
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    return rec_enable(*me, me->lat, 1, raw_cap, MPX_LAT_RAW_MAX, "latency recorder");
+}
+
+int mpx_lat_disable(mpx_ctx* ctx, int rank) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    me->lat.on = false;   // the block stays until finalize (no hipFree between calls)
+    return MPX_OK;
+}
+
+int mpx_lat_reset(mpx_ctx* ctx, int rank) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    if (!me->lat.on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
+    return rec_reset(*me, me->lat);
+}
+
+int mpx_lat_get(mpx_ctx* ctx, int rank, mpx_lat* out) {
+    Rank* me = nullptr;
+    TRY(lat_rank(ctx, rank, &me));
+    if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
+    if (!me->lat.on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
+    return rec_get(*me, me->lat, 0, out);
+}
 
 int mpx_lat_raw(mpx_ctx* ctx, int rank, uint64_t* stamps, int cap, int* n) {
     Rank* me = nullptr;
     TRY(lat_rank(ctx, rank, &me));
     if (!n || cap < 0 || (!stamps && cap > 0)) return fail(MPX_ERR_INVALID, "bad argument");
     *n = 0;
-    if (!me->lat_on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
-    DeviceGuard g(me->dev);
-    HIPCK(g.err);
-    LatBlock h{};
-    TRY(lat_header(*me, &h));
-    // t[0] alone says nothing: with raw_cap = 0 no stamp is reported
-    u64 have = me->lat_cap > 0 ? h.raw_n : 0;
-    if (have > (u64)me->lat_cap + 1) have = (u64)me->lat_cap + 1;
-    if (have > (u64)cap) have = (u64)cap;
-    if (have) {
-        HIPCK(hipMemcpyAsync(stamps, me->lat->raw, (size_t)have * sizeof(u64), hipMemcpyDeviceToHost, me->stream));
-        HIPCK(hipStreamSynchronize(me->stream));
-    }
-    *n = (int)have;
-    return MPX_OK;
+    if (!me->lat.on) return fail(MPX_ERR_STATE, "rank %d: the latency recorder is not enabled", rank);
+    return rec_raw(*me, me->lat, 0, stamps, cap, n);
 }
-
-// ---- per-link latency recorder of the LL fan exchange (include/mpx.h) -------
-namespace {
-// lat_rank's rules (local, no armed call), with this recorder's codes: a rank
-// that is not local is MPX_ERR_INVALID here.
-int fan_lat_rank(mpx_ctx* ctx, int rank, Rank** out) {
-    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
-    if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) return fail(MPX_ERR_INVALID, "rank %d is not a local rank", rank);
-    if (ctx->r[rank].armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", rank);
-    *out = &ctx->r[rank];
-    return MPX_OK;
-}
-int fan_lat_peer(const mpx_ctx* ctx, int rank, int peer) {
-    if (peer < 0 || peer >= ctx->nranks || peer == rank) return fail(MPX_ERR_INVALID, "rank %d: peer rank %d", rank, peer);
-    return MPX_OK;
-}
-size_t fan_lat_stride(const Rank& me) { return lat_block_bytes(me.fan_lat_cap); }
-LatBlock* fan_lat_block(const Rank& me, int peer) {
-    return reinterpret_cast<LatBlock*>(me.fan_lat + (size_t)peer * fan_lat_stride(me));
-}
-// Every peer's block: statistics, histogram and raw count back to zero,
-// raw_cap in force (lat_clear, once per block).
-int fan_lat_clear(const mpx_ctx* ctx, Rank& me) {
-    LatBlock h{};
-    h.raw_cap = (u64)me.fan_lat_cap;
-    for (int p = 0; p < ctx->nranks; ++p)
-        HIPCK(hipMemcpyAsync(fan_lat_block(me, p), &h, offsetof(LatBlock, raw), hipMemcpyHostToDevice, me.stream));
-    HIPCK(hipStreamSynchronize(me.stream));
-    return MPX_OK;
-}
-int fan_lat_header(Rank& me, int peer, LatBlock* h) {
-    HIPCK(hipMemcpyAsync(h, fan_lat_block(me, peer), offsetof(LatBlock, raw), hipMemcpyDeviceToHost, me.stream));
-    HIPCK(hipStreamSynchronize(me.stream));
-    return MPX_OK;
-}
-}  // namespace
 
 int mpx_fan_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
     if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
@@ -1378,45 +1368,21 @@ int mpx_fan_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
         return fail(MPX_ERR_UNSUPPORTED, "the link recorder runs inside the kernel engine's LL fan loop: not this engine");
     Rank* me = nullptr;
     TRY(fan_lat_rank(ctx, rank, &me));
-    if (raw_cap < 0 || raw_cap > MPX_FAN_LAT_RAW_MAX)
-        return fail(MPX_ERR_INVALID, "raw_cap %d not in [0,%d]", raw_cap, MPX_FAN_LAT_RAW_MAX);
-    DeviceGuard g(me->dev);
-    HIPCK(g.err);
-    if (!me->fan_lat || me->fan_lat_alloc < raw_cap) {
-        // (no hipFree here: it waits for the whole device, ensure_csum)
-        const size_t bytes = (size_t)ctx->nranks * lat_block_bytes(raw_cap);
-        void* p = nullptr;
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            return fail(MPX_ERR_NOMEM, "link recorder of %zu B on device %d", bytes, me->dev);
-        }
-        HIPCK(e);
-        if (me->fan_lat) me->retired.push_back(me->fan_lat);
-        me->fan_lat = static_cast<unsigned char*>(p);
-        me->fan_lat_alloc = raw_cap;
-    }
-    me->fan_lat_cap = raw_cap;   // (<= fan_lat_alloc: nranks blocks at this cap's stride fit the allocation)
-    me->fan_lat_on = false;
-    TRY(fan_lat_clear(ctx, *me));
-    me->fan_lat_on = true;
-    return MPX_OK;
+    return rec_enable(*me, me->fan_lat, ctx->nranks, raw_cap, MPX_FAN_LAT_RAW_MAX, "link recorder");
 }
 
 int mpx_fan_lat_disable(mpx_ctx* ctx, int rank) {
     Rank* me = nullptr;
     TRY(fan_lat_rank(ctx, rank, &me));
-    me->fan_lat_on = false;   // the blocks stay until finalize (no hipFree between calls)
+    me->fan_lat.on = false;   // the blocks stay until finalize (no hipFree between calls)
     return MPX_OK;
 }
 
 int mpx_fan_lat_reset(mpx_ctx* ctx, int rank) {
     Rank* me = nullptr;
     TRY(fan_lat_rank(ctx, rank, &me));
-    if (!me->fan_lat_on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
-    DeviceGuard g(me->dev);
-    HIPCK(g.err);
-    return fan_lat_clear(ctx, *me);
+    if (!me->fan_lat.on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
+    return rec_reset(*me, me->fan_lat);
 }
 
 int mpx_fan_lat_get(mpx_ctx* ctx, int rank, int peer, mpx_lat* out) {
@@ -1424,22 +1390,8 @@ int mpx_fan_lat_get(mpx_ctx* ctx, int rank, int peer, mpx_lat* out) {
     TRY(fan_lat_rank(ctx, rank, &me));
     if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
     TRY(fan_lat_peer(ctx, rank, peer));
-    if (!me->fan_lat_on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
-    DeviceGuard g(me->dev);
-    HIPCK(g.err);
-    LatBlock h{};
-    TRY(fan_lat_header(*me, peer, &h));
-    memset(out, 0, sizeof *out);
-    out->count = h.count;
-    out->calls = h.calls;
-    out->min_ticks = h.min_ticks;
-    out->max_ticks = h.max_ticks;
-    out->sum_ticks = h.sum_ticks;
-    out->max_iter = h.max_iter;
-    out->last_iters = h.last_iters;
-    out->tick_s = 1e-8;   // s_memrealtime: 100 MHz
-    memcpy(out->hist, h.hist, sizeof h.hist);
-    return MPX_OK;
+    if (!me->fan_lat.on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
+    return rec_get(*me, me->fan_lat, peer, out);
 }
 
 int mpx_fan_lat_raw(mpx_ctx* ctx, int rank, int peer, uint64_t* stamps, int cap, int* n) {
@@ -1448,22 +1400,8 @@ int mpx_fan_lat_raw(mpx_ctx* ctx, int rank, int peer, uint64_t* stamps, int cap,
     if (!n || cap < 0 || (!stamps && cap > 0)) return fail(MPX_ERR_INVALID, "bad argument");
     *n = 0;
     TRY(fan_lat_peer(ctx, rank, peer));
-    if (!me->fan_lat_on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
-    DeviceGuard g(me->dev);
-    HIPCK(g.err);
-    LatBlock h{};
-    TRY(fan_lat_header(*me, peer, &h));
-    // t[0] alone says nothing: with raw_cap = 0 no stamp is reported
-    u64 have = me->fan_lat_cap > 0 ? h.raw_n : 0;
-    if (have > (u64)me->fan_lat_cap + 1) have = (u64)me->fan_lat_cap + 1;
-    if (have > (u64)cap) have = (u64)cap;
-    if (have) {
-        HIPCK(hipMemcpyAsync(stamps, fan_lat_block(*me, peer)->raw, (size_t)have * sizeof(u64), hipMemcpyDeviceToHost,
-                             me->stream));
-        HIPCK(hipStreamSynchronize(me->stream));
-    }
-    *n = (int)have;
-    return MPX_OK;
+    if (!me->fan_lat.on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
+    return rec_raw(*me, me->fan_lat, peer, stamps, cap, n);
 }
 
 int mpx_barrier(mpx_ctx* ctx, int nthreads) {

@@ -292,6 +292,41 @@ static void write_lat_line(FILE *fp, const mpx_lat *l, const char *ts, int r, in
     fputs(line, fp);
 }
 
+/* The end of every run, pair or fan: MPI_Barrier, the Allreduce of the run's
+   time and, every 1000 runs, rank 0's summary (mpi_perf.c:557-568). */
+static void end_run(int r, long long run_idx, double t_start, double my_time)
+{
+    time_of[r] = my_time;
+    barrier(); /* MPI_Barrier, mpi_perf.c:557 */
+    const double t_end = wtime();
+    /* Allreduce MIN/MAX/SUM, mpi_perf.c:560-562 (every run, every rank) */
+    double mn = my_time, mx = my_time, sum = my_time;
+    if (procs) {
+        if (mpxb_allreduce_f64(boot, my_time, &mn, &mx, &sum) != 0) boot_failed();
+    } else if (r == 0) {
+        /* the other threads cannot overwrite time_of before rank 0
+           reaches the next run's barrier */
+        sum = 0;
+        for (int q = 0; q < world; ++q) {
+            if (time_of[q] < mn) mn = time_of[q];
+            if (time_of[q] > mx) mx = time_of[q];
+            sum += time_of[q];
+        }
+    }
+    if (r == 0 && (run_idx % 1000 == 0)) { /* mpi_perf.c:564-568 */
+        char line[256];
+        mpxh_format_summary(line, sizeof line, run_idx, t_end - t_start, mn, mx, sum, world);
+        fputs(line, stderr);
+    }
+}
+
+static void close_logs(rank_files *f)
+{
+    if (f->log_fp) fclose(f->log_fp);
+    if (f->gpu_fp) fclose(f->gpu_fp);
+    if (f->lat_fp) fclose(f->lat_fp);
+}
+
 /* the run loop of one rank, mpi_perf.c:470-569 */
 static void *rank_main(void *arg)
 {
@@ -393,33 +428,10 @@ static void *rank_main(void *arg)
                 }
             }
 
-            time_of[r] = my_time;
-            barrier(); /* MPI_Barrier, mpi_perf.c:557 */
-            const double t_end = wtime();
-            /* Allreduce MIN/MAX/SUM, mpi_perf.c:560-562 (every run, every rank) */
-            double mn = my_time, mx = my_time, sum = my_time;
-            if (procs) {
-                if (mpxb_allreduce_f64(boot, my_time, &mn, &mx, &sum) != 0) boot_failed();
-            } else if (r == 0) {
-                /* the other threads cannot overwrite time_of before rank 0
-                   reaches the next run's barrier */
-                sum = 0;
-                for (int q = 0; q < world; ++q) {
-                    if (time_of[q] < mn) mn = time_of[q];
-                    if (time_of[q] > mx) mx = time_of[q];
-                    sum += time_of[q];
-                }
-            }
-            if (r == 0 && (run_idx % 1000 == 0)) { /* mpi_perf.c:564-568 */
-                char line[256];
-                mpxh_format_summary(line, sizeof line, run_idx, t_end - t_start, mn, mx, sum, world);
-                fputs(line, stderr);
-            }
+            end_run(r, run_idx, t_start, my_time);
         }
     }
-    if (files.log_fp) fclose(files.log_fp);
-    if (files.gpu_fp) fclose(files.gpu_fp);
-    if (files.lat_fp) fclose(files.lat_fp);
+    close_logs(&files);
     return NULL;
 }
 
@@ -516,30 +528,10 @@ static void *rank_main_fan(void *arg)
                 }
             }
 
-            time_of[r] = my_time;
-            barrier(); /* MPI_Barrier, mpi_perf.c:557 */
-            const double t_end = wtime();
-            double mn = my_time, mx = my_time, sum = my_time; /* Allreduce MIN/MAX/SUM, mpi_perf.c:560-562 */
-            if (procs) {
-                if (mpxb_allreduce_f64(boot, my_time, &mn, &mx, &sum) != 0) boot_failed();
-            } else if (r == 0) {
-                sum = 0;
-                for (int q = 0; q < world; ++q) {
-                    if (time_of[q] < mn) mn = time_of[q];
-                    if (time_of[q] > mx) mx = time_of[q];
-                    sum += time_of[q];
-                }
-            }
-            if (r == 0 && (run_idx % 1000 == 0)) { /* mpi_perf.c:564-568 */
-                char line[256];
-                mpxh_format_summary(line, sizeof line, run_idx, t_end - t_start, mn, mx, sum, world);
-                fputs(line, stderr);
-            }
+            end_run(r, run_idx, t_start, my_time);
         }
     }
-    if (files.log_fp) fclose(files.log_fp);
-    if (files.gpu_fp) fclose(files.gpu_fp);
-    if (files.lat_fp) fclose(files.lat_fp);
+    close_logs(&files);
     return NULL;
 }
 

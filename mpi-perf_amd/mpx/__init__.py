@@ -456,6 +456,20 @@ class Context:
         check(self.L.mpx_test_advance_link(self.h, my_rank, peer_rank, seq_by, calls_by, token_by),
               "mpx_test_advance_link")
 
+    # the two latency recorders' reads: `key` is (rank,) or (rank, peer)
+    def _lat_dict(self, fn: str, *key: int) -> dict:
+        l = Lat()
+        check(getattr(self.L, fn)(self.h, *key, C.byref(l)), fn)
+        return l.as_dict()
+
+    def _lat_stamps(self, fn: str, caps: dict, cap: int | None, *key: int) -> list[int]:
+        if cap is None:
+            cap = caps.get(key[0], 0) + 1
+        n = C.c_int(0)
+        buf = (C.c_uint64 * max(cap, 1))()
+        check(getattr(self.L, fn)(self.h, *key, buf, cap, C.byref(n)), fn)
+        return list(buf[:n.value])
+
     # per-iteration latency recorder (kernel engine)
     def lat_enable(self, rank: int, raw_cap: int = 0) -> None:
         """mpx_lat_enable: trace rank's ping-pong / unidir calls from now on,
@@ -471,19 +485,12 @@ class Context:
 
     def lat_get(self, rank: int) -> dict:
         """mpx_lat_get: the distribution accumulated since enable / reset"""
-        l = Lat()
-        check(self.L.mpx_lat_get(self.h, rank, C.byref(l)), "mpx_lat_get")
-        return l.as_dict()
+        return self._lat_dict("mpx_lat_get", rank)
 
     def lat_raw(self, rank: int, cap: int | None = None) -> list[int]:
         """mpx_lat_raw: the last traced call's stamps t[0 .. min(iters, raw_cap)]
         (cap: at most that many; default all of them)"""
-        if cap is None:
-            cap = self._lat_cap.get(rank, 0) + 1
-        n = C.c_int(0)
-        buf = (C.c_uint64 * max(cap, 1))()
-        check(self.L.mpx_lat_raw(self.h, rank, buf, cap, C.byref(n)), "mpx_lat_raw")
-        return list(buf[:n.value])
+        return self._lat_stamps("mpx_lat_raw", self._lat_cap, cap, rank)
 
     # per-link latency recorder of the lock-step LL fan exchange (kernel engine)
     def fan_lat_enable(self, rank: int, raw_cap: int = 0) -> None:
@@ -501,19 +508,12 @@ class Context:
     def fan_lat_get(self, rank: int, peer: int) -> dict:
         """mpx_fan_lat_get: link (rank, peer)'s distribution since enable /
         reset (the dict of lat_get; blocks are keyed by the peer's rank)"""
-        l = Lat()
-        check(self.L.mpx_fan_lat_get(self.h, rank, peer, C.byref(l)), "mpx_fan_lat_get")
-        return l.as_dict()
+        return self._lat_dict("mpx_fan_lat_get", rank, peer)
 
     def fan_lat_raw(self, rank: int, peer: int, cap: int | None = None) -> list[int]:
         """mpx_fan_lat_raw: link (rank, peer)'s stamps t[0 .. min(iters, raw_cap)]
         of the last traced call that listed peer (cap: at most that many)"""
-        if cap is None:
-            cap = self._fan_lat_cap.get(rank, 0) + 1
-        n = C.c_int(0)
-        buf = (C.c_uint64 * max(cap, 1))()
-        check(self.L.mpx_fan_lat_raw(self.h, rank, peer, buf, cap, C.byref(n)), "mpx_fan_lat_raw")
-        return list(buf[:n.value])
+        return self._lat_stamps("mpx_fan_lat_raw", self._fan_lat_cap, cap, rank, peer)
 
     def rccl_init_all(self) -> None:
         check(self.L.mpx_rccl_init_all(self.h), "mpx_rccl_init_all")

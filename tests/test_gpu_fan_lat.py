@@ -1,4 +1,4 @@
-"""The link recorder (mpx_fan_lat_*, k_xfer_fan_ll_lat) on the GPU: loopback
+"""The link recorder (mpx_fan_lat_*, k_xfer_fan_ll's traced form) on the GPU: loopback
 ranks on GPU 0 (tests/fan_ll.py).
 
 Lane 0 of every workgroup of a traced MPX_FAN_LL call — workgroup k IS link k —
@@ -25,6 +25,7 @@ import pytest
 
 import mpx
 import oracle_py as O
+import payload
 from fan import full_mesh
 from fan_ll import LLFan, mesh
 
@@ -383,6 +384,31 @@ def test_enabling_again_with_a_larger_cap_regrows():
         enable_all(F, MESH3, 2048)
         out = F.checked_call(MESH3, 600, True, "cap 2048")
         check_every_link(F, MESH3, out, 600, "regrown")
+    finally:
+        F.close()
+
+
+def test_enabling_again_with_a_smaller_cap_keeps_the_blocks_apart():
+    """cap 64, then cap 2: the allocation stays and the blocks' stride shrinks,
+    for the host and the kernel alike — every link's block holds its own call.
+    Three attached ranks in a context of four: rank 3 is never listed, so its
+    block, the last at the new stride, reads zeros on every rank.  (A rank's OWN
+    block has no reader: peer == rank is MPX_ERR_INVALID.)"""
+    iters = 5
+    F = LLFan(4, 4 * 16 + payload.GUARD, ranks=[0, 1, 2])
+    F.layout(8, 16)
+    try:
+        enable_all(F, MESH3, 64)
+        enable_all(F, MESH3, 2)
+        F.checked_call(MESH3, iters, True, "cap 64, then 2")
+        for r, p in ((r, p) for r in MESH3 for p in MESH3[r]):
+            lat, raw = F.c.fan_lat_get(r, p), F.c.fan_lat_raw(r, p)
+            assert len(raw) == 3 and raw[0] <= raw[1] <= raw[2], (r, p, raw)
+            assert lat["count"] == iters and lat["calls"] == 1 and lat["last_iters"] == iters, (r, p, lat)
+            assert sum(lat["hist"]) == iters and lat["sum_ticks"] >= raw[2] - raw[0], (r, p, lat)
+        for r in MESH3:
+            assert is_zero(F.c.fan_lat_get(r, 3)) and F.c.fan_lat_raw(r, 3) == []
+            assert status_of(lambda: F.c.fan_lat_get(r, r)) == mpx.ERR_INVALID
     finally:
         F.close()
 

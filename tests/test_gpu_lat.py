@@ -149,6 +149,28 @@ def test_accumulate_reset_disable(pair):
         assert {f: getattr(out[r], f) for f in RESULT_FIELDS} == want[r]
 
 
+def test_enabling_again_with_a_larger_cap_regrows():
+    """a context of its own, so that the block is first allocated for cap 4:
+    cap 64 takes a new block (the old one retires), and enable clears"""
+    P = Pairs("kernel", 1, B_LL)
+    try:
+        for cap in (4, 64):
+            for r in (0, 1):
+                P.c.lat_enable(r, cap)
+            out, errs = P.run(mpx.MODE_PINGPONG, B_LL, 6)
+            assert not errs, errs
+            if cap == 4:
+                assert all(len(P.c.lat_raw(r)) == 5 for r in (0, 1))
+        for r in (0, 1):
+            raw, lat = P.c.lat_raw(r), P.c.lat_get(r)
+            assert len(raw) == 7
+            assert lat["count"] == 6 and lat["calls"] == 1 and lat["last_iters"] == 6 and sum(lat["hist"]) == 6
+            assert lat["sum_ticks"] == raw[-1] - raw[0] == sum(b - a for a, b in zip(raw, raw[1:]))
+            assert out[r].check_failures == 0 and out[r].check_iters == 6
+    finally:
+        P.close()
+
+
 def test_a_stalled_iteration_is_attributed_to_its_index(pair, monkeypatch):
     """positive control: rank 1's last workgroup stalls 20 ms before pulling
     the call's last payload (MPX_TEST lag_wg), so iteration 19 of 20 — and only
