@@ -249,7 +249,11 @@ int mpx_read(mpx_ctx *ctx, int dev, void *host_dst, const void *dev_src, size_t 
 
 /* ---- local device-to-device copy (BASELINE config 2) --------------------- */
 /* `iters` back-to-back launches of the HBM copy kernel dst[0:n) = src[0:n) on
-   `dev`; the 1-GPU degenerate case of the loop (tx -> rx, no peer). */
+   `dev`; the 1-GPU degenerate case of the loop (tx -> rx, no peer).  Each of
+   the `iters` copies loads src anew and stores all of dst, also where all of
+   them run in one launch (tests/test_gpu_live_copy.py).  src must not change
+   during the call: inside one launch a load may be served from the GPU's
+   caches. */
 int mpx_copy(mpx_ctx *ctx, int dev, void *dst, const void *src, size_t n, int iters,
              mpx_timing *t);
 

@@ -82,10 +82,10 @@ class Pairs:
         return self.c.checksum(tx, n), self.c.checksum(tx, 1)
 
     def run(self, mode, n, iters, check=True, timeout_ms=10000, ranks=None, nwg=0, stream=False, pull=False,
-            armed=False):
+            armed=False, stage=True):
         """every rank's side on a thread of its own; armed: each side arms
         its call (mpx_xfer_arm), all sides meet at a barrier (the hosts'
-        mpi_perf.c:499), then start it"""
+        mpi_perf.c:499), then start it; stage=False: MPX_XFER_NOSTAGE"""
         ranks = list(self.ranks) if ranks is None else ranks
         exp = {r: self.expect(r, n) for r in ranks}
         out, errs = {}, {}
@@ -93,7 +93,7 @@ class Pairs:
 
         def side(r):
             kw = dict(check_payload=check, expect=exp[r][0], expect_ack=exp[r][1], timeout_ms=timeout_ms, nwg=nwg,
-                      stream=stream, pull=pull)
+                      stream=stream, pull=pull, stage=stage)
             args = (mode, self.group(r), r, self.peer(r), iters, self.bufs[r][0], self.bufs[r][1], n)
             try:
                 if armed:
