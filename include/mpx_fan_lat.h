@@ -41,7 +41,7 @@
      - The recorder never makes a transfer fail.  A call that fails (timeout,
        check) leaves the contents undefined until mpx_fan_lat_reset.
      - With the recorder off an LL fan call runs the kernels it ran before:
-       traced calls run kernels of their own (k_xfer_fan_ll_lat).
+       traced calls run instantiations of their own (k_xfer_fan_ll<., true>).
    The ABI version is unchanged: callers detect the feature by symbol. */
 #define MPX_FAN_LAT_RAW_MAX (1 << 16)   /* largest raw_cap mpx_fan_lat_enable accepts */
 /* raw_cap: stamps kept per link and call beyond t[0]; allocates nranks blocks

@@ -1,9 +1,12 @@
 // mpx_engine_stream.hip — the two stream engines behind mpx_xfer_ex: SDMA
 // (run_sdma) and RCCL (run_rccl, with its run-time loader and the mpx_rccl_*
 // entry points), and what prepares them ahead of a call (mpx_xfer_prepare).
-// Both enqueue their loop on the rank's stream between one begin
-// (stream_begin) and one end (stream_end).
+// Both enqueue ONE loop, mpx_stream_loop.h's, on the rank's stream between one
+// begin (stream_begin) and one end (stream_end); what an iteration enqueues is
+// in four operations objects: SdmaPush, SdmaPull, SdmaNbChecked and RcclOps
+// (DESIGN.md "Stream engines").
 #include "mpx_runtime.h"
+#include "mpx_stream_loop.h"
 
 using namespace mpx;
 
@@ -115,10 +118,6 @@ int stream_end(Rank& me, int check, int mode, int iters, double t0, int launches
     return MPX_OK;
 }
 
-// ---------------------------------------------------------------------------
-// engine: SDMA — hipMemcpyAsync into the peer's rx, then a one-lane flag
-// store; the receiver's stream waits on its mailbox flag with a one-lane poll.
-// ---------------------------------------------------------------------------
 // check mode for the stream engines: checksum the received bytes into
 // csum[i], then poison them — stream-ordered before the next push.
 int stream_check(Rank& me, long long n, int i, int iters, unsigned char* buf = nullptr) {
@@ -130,6 +129,23 @@ int stream_check(Rank& me, long long n, int i, int iters, unsigned char* buf = n
     return MPX_OK;
 }
 
+// What every operations object (mpx_stream_loop.h) has of its rank: the
+// launches it counts, check mode's per-receive checksum, and the device-side
+// receive accounting (neither counted).
+struct RankOps {
+    Rank& me;
+    int launches = 0;   // mpx_timing.launches of the loop
+    int check(long long n, int i, int iters) { return stream_check(me, n, i, iters); }
+    int account(int j0, int count, long long n) {
+        HIPCK(launch_account(me.status, me.csum, j0, count, n, me.stream));
+        return MPX_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// engine: SDMA — hipMemcpyAsync into the peer's rx, then a one-lane flag
+// store; the receiver's stream waits on its mailbox flag with a one-lane poll.
+// ---------------------------------------------------------------------------
 // The SDMA engine's payload copy kind.  Between two GPUs it is
 // hipMemcpyDeviceToDeviceNoCU: the runtime must use a copy engine (SDMA), the
 // engine north_star (b) names.  Within one GPU (loopback pairs) it is the
@@ -141,209 +157,121 @@ int stream_check(Rank& me, long long n, int i, int iters, unsigned char* buf = n
 // (profiles/r02_sdma_kind_ab.jsonl), which also moved 40 GB/s against the
 // blit kernel's 570 on one GPU.  A rank paired with itself has one stream and
 // cannot deadlock so.  MPX_SDMA_KIND=nocu|blit forces one kind (A/B).
-hipMemcpyKind sdma_kind(bool same_gpu) {
+hipMemcpyKind sdma_kind(const Rank& me, const Rank& peer) {
     static const int forced = [] {
         const char* v = getenv("MPX_SDMA_KIND");
         return !v ? 0 : !strcmp(v, "nocu") ? 1 : !strcmp(v, "blit") ? 2 : 0;
     }();
+    const bool same_gpu = &me != &peer && same_device(me, peer);   // distinct ranks of one GPU
     const bool nocu = forced == 1 || (forced == 0 && !same_gpu);
     return nocu ? hipMemcpyDeviceToDeviceNoCU : hipMemcpyDeviceToDevice;
 }
 
-// non-blocking publish schedule shared by the kernel and SDMA engines: every
-// nb_publish() pushes, at window slot 254 (the last receive a Waitall(255)
-// waits for, so no flush waits for the slot-255 push the reference leaves
-// pending) and at the last push
-bool nb_publishes(int i, int iters) {
-    return (i + 1) % nb_publish() == 0 || i % kNbWindow == kNbWindow - 2 || i + 1 == iters;
-}
-
-struct SdmaOps {
-    Rank& me;
+// The SDMA engine's primitives; each counts one launch when it enqueues.
+// Push number i + 1 of the call is tx0 + i + 1 on this side's sends, rx0 +
+// i + 1 on the peer's.
+struct SdmaOps : RankOps {
     Rank& peer;
     int my_slot, peer_slot;
     u64 tmo;
+    u64 tx0, rx0;               // the link's push numbers before the call
     const u64* txb = nullptr;   // graph capture: seqs relative to these device words
     const u64* rxb = nullptr;
-    int launches = 0;
-    int skip = 0;               // test knob: 1 + iteration whose copy is skipped
-    bool pull = false;          // MPX_XFER_PULL: B-byte payloads copied by the receiver's stream
+    int copy(void* dst, const void* src, long long n, bool lost) {
+        if (n <= 0 || lost) return MPX_OK;
+        HIPCK(hipMemcpyAsync(dst, src, (size_t)n, sdma_kind(me, peer), me.stream));
+        ++launches;
+        return MPX_OK;
+    }
     // The flag store is a one-lane kernel ordered after the copy on this
     // stream (hipStreamWriteValue64 measured slower, 10.9 vs 8.6 us per
     // iteration, profiles/r01_sdma_signal_ab.jsonl).  Waits are bounded
     // one-lane kernels: a stream-level wait (hipStreamWaitValue64) cannot
-    // time out.
-    int push(long long n, u64 seq, bool publish = true, bool skip_copy = false) {
-        if (n > 0 && !skip_copy) {
-            HIPCK(hipMemcpyAsync(peer.rx, me.tx, (size_t)n, sdma_kind(&me != &peer && same_device(me, peer)),
-                                 me.stream));
-            ++launches;
-        }
-        if (!publish) return MPX_OK;
-        HIPCK(launch_signal(&peer.mb->flag[my_slot][0], txb, seq, me.stream));
+    // time out.  base: the capture's sequence base (txb / rxb), or null.
+    int signal(u64* flag, const u64* base, u64 v) {
+        HIPCK(launch_signal(flag, base, v, me.stream));
         ++launches;
         return MPX_OK;
     }
-    int wait(u64 seq) {
-        HIPCK(launch_wait(&me.mb->flag[peer_slot][0], rxb, seq, me.status, tmo, me.stream));
+    int wait(const u64* flag, const u64* base, u64 v) {
+        HIPCK(launch_wait(flag, base, v, me.status, tmo, me.stream));
         ++launches;
         return MPX_OK;
     }
-    // Pull mode (the kernel engine's k_xfer_pull in stream form).  A send
-    // publishes "tx holds push seq" in the peer's ready word (tx is read-only
-    // while the loop runs, and the reference re-sends the same buffer).
-    int pull_send(u64 seq) {
-        HIPCK(launch_signal(&peer.mb->ready[my_slot], txb, seq, me.stream));
-        ++launches;
-        return MPX_OK;
-    }
-    // A receive waits for the peer's ready word, copies the peer's tx into rx
-    // on this rank's stream (a copy engine reading the peer's HBM across
-    // GPUs), then, when `publish`, hands the peer's tx back (credit = seq,
-    // for every push up to seq).
-    int pull_recv(long long n, u64 seq, bool publish, bool skip_copy) {
-        HIPCK(launch_wait(&me.mb->ready[peer_slot], rxb, seq, me.status, tmo, me.stream));
-        ++launches;
-        if (n > 0 && !skip_copy) {
-            HIPCK(hipMemcpyAsync(me.rx, peer.tx, (size_t)n, sdma_kind(&me != &peer && same_device(me, peer)),
-                                 me.stream));
-            ++launches;
-        }
-        if (!publish) return MPX_OK;
-        HIPCK(launch_signal(&peer.mb->credit[my_slot][0], rxb, seq, me.stream));
-        ++launches;
-        return MPX_OK;
-    }
-    // every one of this side's sends up to `seq` copied by the peer
-    int wait_pulled(u64 seq) {
-        HIPCK(launch_wait(&me.mb->credit[peer_slot][0], txb, seq, me.status, tmo, me.stream));
-        ++launches;
-        return MPX_OK;
-    }
-    // one iteration of the pulled loop (see step)
-    int pull_step(int mode, int group, long long len, int i, int iters, u64 tx0, u64 rx0, bool check, int* inflight) {
-        const bool sk = skip == i + 1;
-        if (mode == MPX_MODE_PINGPONG) {
-            if (group == 1) {
-                TRY(pull_send(tx0 + i + 1));
-                TRY(pull_recv(len, rx0 + i + 1, true, sk));
-                if (check) TRY(stream_check(me, len, i, iters));
-            } else {
-                TRY(pull_recv(len, rx0 + i + 1, true, sk));
-                if (check) TRY(stream_check(me, len, i, iters));
-                TRY(pull_send(tx0 + i + 1));
-            }
-        } else if (mode == MPX_MODE_UNIDIR) {
-            if (group == 1) {
-                TRY(pull_send(tx0 + i + 1));
-                TRY(wait(rx0 + i + 1));                      // the 1-byte ack, pushed
-                if (check) TRY(stream_check(me, 1, i, iters));
-            } else {
-                TRY(pull_recv(len, rx0 + i + 1, true, sk));
-                if (check) TRY(stream_check(me, len, i, iters));
-                TRY(push(1, tx0 + i + 1, true, false));      // Send(tx, 1): always one byte, pushed
-            }
-        } else {
-            // Isend + Irecv; the receive is complete on this stream once its
-            // copy ran; credits go back on the push's publish schedule
-            TRY(pull_send(tx0 + i + 1));
-            TRY(pull_recv(len, rx0 + i + 1, nb_publishes(i, iters), sk));
-            if (check) TRY(stream_check(me, len, i, iters));
-            if (*inflight == kNbWindow - 1) {
-                // Waitall(255): the peer's copies of sends 0..254; the
-                // receives of slots 0..254 are done (stream order) — count them
-                TRY(wait_pulled(tx0 + i));
-                if (check) HIPCK(launch_account(me.status, me.csum, i - *inflight, *inflight, len, me.stream));
-                *inflight = 0;
-            } else {
-                ++*inflight;
-            }
-        }
-        return MPX_OK;
-    }
-    // one iteration i of the loop (mpi_perf.c:70-82, 95-124, 132-144), seqs
-    // relative to tx0 / rx0; check mode checksums + poisons each received
-    // payload where the reference's Recv returns (before the reply / ack);
-    // *inflight is the non-blocking window fill
-    int step(int mode, int group, long long len, int i, int iters, u64 tx0, u64 rx0, bool check, int* inflight) {
-        if (pull) return pull_step(mode, group, len, i, iters, tx0, rx0, check, inflight);
-        const bool sk = skip == i + 1;
-        if (mode == MPX_MODE_PINGPONG) {
-            if (group == 1) {
-                TRY(push(len, tx0 + i + 1, true, sk));
-                TRY(wait(rx0 + i + 1));
-                if (check) TRY(stream_check(me, len, i, iters));
-            } else {
-                TRY(wait(rx0 + i + 1));
-                if (check) TRY(stream_check(me, len, i, iters));
-                TRY(push(len, tx0 + i + 1, true, sk));
-            }
-        } else if (mode == MPX_MODE_UNIDIR) {
-            if (group == 1) {
-                TRY(push(len, tx0 + i + 1, true, sk));
-                TRY(wait(rx0 + i + 1));
-                if (check) TRY(stream_check(me, 1, i, iters));
-            } else {
-                TRY(wait(rx0 + i + 1));
-                if (check) TRY(stream_check(me, len, i, iters));
-                TRY(push(1, tx0 + i + 1, true, sk));        // Send(tx, 1): always one byte
-            }
-        } else {
-            TRY(push(len, tx0 + i + 1, nb_publishes(i, iters), sk));
-            if (*inflight == kNbWindow - 1) {
-                TRY(wait(rx0 + i));                          // Waitall(255): not slot 255's receive
-                *inflight = 0;
-            } else {
-                ++*inflight;
-            }
-        }
-        return MPX_OK;
-    }
+};
 
-    // The non-blocking loop in check mode, stream-ordered (the kernel
-    // engine's k_xfer_nbcheck in host-enqueued form): receive i lands in slot
-    // ring_slot(i) of the receiver; before a push reuses a slot the sender's
-    // stream waits for the receiver's credit; each receive is waited for,
-    // checksummed and poisoned right after this side's push i (so the two
-    // streams never wait on each other in a cycle), and the device counts
-    // the reference's Waitall receives (k_account at each flush).
-    // The call's receives were posted (Mailbox.posted) before it starts, so
-    // the first `slots` pushes need no credit.
-    int nb_checked(int iters, long long len, u64 tx0, u64 rx0, int slots) {
-        u64* credit_out = &peer.mb->credit[my_slot][0];
-        const u64* credit_in = &me.mb->credit[peer_slot][0];
-        int inflight = 0;
-        for (int i = 0; i < iters; ++i) {
-            if (i >= slots) TRY(wait_abs(credit_in, tx0 + (u64)(i - slots + 1)));
-            if (len > 0 && skip != i + 1) {
-                HIPCK(hipMemcpyAsync(slot_ptr(peer, i, iters, slots, len), me.tx, (size_t)len,
-                                     sdma_kind(same_device(me, peer) && &me != &peer), me.stream));
-                ++launches;
-            }
-            TRY(signal_abs(&peer.mb->flag[my_slot][0], tx0 + i + 1));
-            TRY(wait_abs(&me.mb->flag[peer_slot][0], rx0 + i + 1));
-            TRY(stream_check(me, len, i, iters, slot_ptr(me, i, iters, slots, len)));
-            TRY(signal_abs(credit_out, rx0 + i + 1));
-            if (inflight == kNbWindow - 1) {          // Waitall(255): iterations i-255 .. i-1
-                HIPCK(launch_account(me.status, me.csum, i - inflight, inflight, len, me.stream));
-                inflight = 0;
-            } else {
-                ++inflight;
-            }
-        }
-        if (inflight > 0) HIPCK(launch_account(me.status, me.csum, iters - inflight, inflight, len, me.stream));
-        return MPX_OK;
+// Pushed: a send copies tx into the peer's rx and, when `publish`, stores the
+// push's number into the peer's flag; a receive waits for this rank's flag.
+struct SdmaPush : SdmaOps {
+    int send(long long n, int i, bool publish, bool lost, bool /*ack*/) {
+        TRY(copy(peer.rx, me.tx, n, lost));
+        return publish ? signal(&peer.mb->flag[my_slot][0], txb, tx0 + i + 1) : MPX_OK;
     }
-    int signal_abs(u64* flag, u64 v) {
-        HIPCK(launch_signal(flag, nullptr, v, me.stream));
-        ++launches;
-        return MPX_OK;
+    int recv(long long, int i, bool, bool, bool) { return wait(&me.mb->flag[peer_slot][0], rxb, rx0 + i + 1); }
+    int nb_post(long long n, int i, bool publish, bool lost) { return send(n, i, publish, lost, false); }
+    int nb_flush(int i, int) { return wait(&me.mb->flag[peer_slot][0], rxb, rx0 + i); }   // not slot 255's receive
+    int drain(const StreamCall& c, int inflight) {                           // the final Waitall(inflight)
+        return c.mode == MPX_MODE_NONBLOCKING && inflight > 0 ? nb_flush(c.iters, inflight) : MPX_OK;
     }
-    int wait_abs(const u64* flag, u64 v) {
-        HIPCK(launch_wait(flag, nullptr, v, me.status, tmo, me.stream));
-        ++launches;
-        return MPX_OK;
+};
+
+// Pulled (MPX_XFER_PULL; the kernel engine's k_xfer_pull in stream form).  A
+// send publishes "tx holds push seq" in the peer's ready word (tx is read-only
+// while the loop runs, and the reference re-sends the same buffer).  A receive
+// waits for the peer's ready word, copies the peer's tx into rx on this rank's
+// stream (a copy engine reading the peer's HBM across GPUs), then, when
+// `publish`, hands the peer's tx back (credit = seq, for every push up to
+// seq).  Unidir's 1-byte ack stays a push, and is never the lost payload.
+struct SdmaPull : SdmaPush {
+    int send(long long n, int i, bool, bool, bool ack) {
+        if (ack) return SdmaPush::send(n, i, true, false, true);
+        return signal(&peer.mb->ready[my_slot], txb, tx0 + i + 1);
     }
+    int recv(long long n, int i, bool publish, bool lost, bool ack) {
+        if (ack) return SdmaPush::recv(n, i, true, false, true);
+        TRY(wait(&me.mb->ready[peer_slot], rxb, rx0 + i + 1));
+        TRY(copy(me.rx, peer.tx, n, lost));
+        return publish ? signal(&peer.mb->credit[my_slot][0], rxb, rx0 + i + 1) : MPX_OK;
+    }
+    // Isend + Irecv; the receive is complete on this stream once its copy
+    // ran; credits go back on the push's publish schedule
+    int nb_post(long long n, int i, bool publish, bool lost) {
+        TRY(send(n, i, true, false, false));
+        return recv(n, i, publish, lost, false);
+    }
+    // every one of this side's sends up to tx0 + i copied by the peer.
+    // Waitall(255): the peer's copies of sends 0..254; the receives of slots
+    // 0..254 are done (stream order)
+    int nb_flush(int i, int) { return wait(&me.mb->credit[peer_slot][0], txb, tx0 + i); }
+    // a side that sent B-byte payloads waits for the peer's copies of its tx
+    int drain(const StreamCall& c, int) {
+        return c.mode != MPX_MODE_UNIDIR || c.group == 1 ? nb_flush(c.iters, 0) : MPX_OK;
+    }
+};
+
+// The non-blocking loop in check mode, stream-ordered (the kernel engine's
+// k_xfer_nbcheck in host-enqueued form): receive i lands in slot ring_slot(i)
+// of the receiver; before a push reuses a slot the sender's stream waits for
+// the receiver's credit; each receive is waited for, checksummed and poisoned
+// right after this side's push i (so the two streams never wait on each other
+// in a cycle), then its slot is handed back (the credit), and the device
+// counts the reference's Waitall receives (account at each flush).  The call's
+// receives were posted (Mailbox.posted) before it starts, so the first `slots`
+// pushes need no credit.  Sequence numbers are absolute: never captured.
+struct SdmaNbChecked : SdmaPush {
+    int iters, slots;
+    int nb_post(long long n, int i, bool, bool lost) {
+        if (i >= slots) TRY(wait(&me.mb->credit[peer_slot][0], nullptr, tx0 + (u64)(i - slots + 1)));
+        TRY(copy(slot_ptr(peer, i, iters, slots, n), me.tx, n, lost));
+        TRY(signal(&peer.mb->flag[my_slot][0], nullptr, tx0 + i + 1));
+        return wait(&me.mb->flag[peer_slot][0], nullptr, rx0 + i + 1);
+    }
+    int check(long long n, int i, int) {
+        TRY(stream_check(me, n, i, iters, slot_ptr(me, i, iters, slots, n)));
+        return signal(&peer.mb->credit[my_slot][0], nullptr, rx0 + i + 1);
+    }
+    int nb_flush(int, int) { return MPX_OK; }   // every receive was waited for where it was checked
+    int drain(const StreamCall&, int) { return MPX_OK; }
 };
 
 // Graph-captured chunks of the SDMA loop (no check mode): the host enqueues
@@ -367,6 +295,15 @@ bool sdma_graphs_enabled() {
     return on;
 }
 
+// what a call of `iters` iterations replays: full chunks, and the remainder
+// if it is worth a graph (not in check mode, whose per-iteration checksum
+// slots would move with every chunk)
+struct SdmaSplit { int chunks, rest; };
+SdmaSplit sdma_split(int iters, bool check) {
+    if (check || !sdma_graphs_enabled() || iters < kSdmaGraphMin) return {0, 0};
+    return {iters / kSdmaChunk, iters % kSdmaChunk >= kSdmaGraphMin ? iters % kSdmaChunk : 0};
+}
+
 int sdma_chunk_graph(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int group, long long len,
                      u64 tmo, int count, hipGraphExec_t* out, bool pull = false) {
     const SdmaKey key{mode + (pull ? 8 : 0), group, peer_rank, len, tmo, count};
@@ -375,11 +312,12 @@ int sdma_chunk_graph(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode,
         *out = it->second;
         return MPX_OK;
     }
-    SdmaOps cap{me, peer, my_rank, peer_rank, tmo, me.scratch + kScrSeqBase, me.scratch + kScrSeqBase + 1};
-    cap.pull = pull;
+    const StreamCall c{mode, group, len, count, false, nb_publish(), 0};
+    SdmaPush push{{{me}, peer, my_rank, peer_rank, tmo, 0, 0, me.scratch + kScrSeqBase, me.scratch + kScrSeqBase + 1}};
+    SdmaPull pulled{push};
     HIPCK(hipStreamBeginCapture(me.stream, hipStreamCaptureModeThreadLocal));
-    int inflight = 0, st = MPX_OK;
-    for (int j = 0; j < count && st == MPX_OK; ++j) st = cap.step(mode, group, len, j, count, 0, 0, false, &inflight);
+    int inflight = 0;
+    int st = pull ? stream_loop(pulled, c, 0, count, &inflight) : stream_loop(push, c, 0, count, &inflight);
     if (st == MPX_OK) st = launch_seqbase(me.scratch + kScrSeqBase, count, count, 1, me.stream) == hipSuccess
                                ? MPX_OK : fail(MPX_ERR_HIP, "k_seqbase launch in capture");
     hipGraph_t g = nullptr;
@@ -402,61 +340,45 @@ int sdma_chunk_graph(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode,
 
 int run_sdma(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int group, int iters, long long len,
              const mpx_xfer_opts* o, mpx_timing* t, bool pull) {
-    SdmaOps op{me, peer, my_rank, peer_rank, timeout_ticks(o)};
-    op.skip = test_knobs().skip_push;
-    op.pull = pull;
     const int check = (o && o->check) ? 1 : 0;
     const int slots = link_slots(me, peer, len);
-    if (!pull && check && mode == MPX_MODE_NONBLOCKING && len > 0 && slots > 1 && (!me.ring || !peer.ring))
+    const bool nbcheck = !pull && check && mode == MPX_MODE_NONBLOCKING;
+    if (nbcheck && len > 0 && slots > 1 && (!me.ring || !peer.ring))
         return fail(MPX_ERR_STATE, "rank %d/%d: check-mode receive ring missing", my_rank, peer_rank);
     const u64 txs0 = me.tx_seq[peer_rank], rxs0 = me.rx_seq[peer_rank];
-    // graph-replayed chunks for the bulk of the loop (not in check mode,
-    // whose per-iteration checksum slots would move with every chunk)
-    const bool graphs = !check && sdma_graphs_enabled() && iters >= kSdmaGraphMin;
-    const int chunks = graphs ? iters / kSdmaChunk : 0;
-    const int rest = graphs && iters % kSdmaChunk >= kSdmaGraphMin ? iters % kSdmaChunk : 0;
+    const StreamCall c{mode, group, len, iters, check != 0, nb_publish(), test_knobs().skip_push};
+    const SdmaPush push{{{me}, peer, my_rank, peer_rank, timeout_ticks(o), txs0, rxs0}};
+    // graph-replayed chunks for the bulk of the loop
+    const SdmaSplit sp = sdma_split(iters, check);
     hipGraphExec_t full = nullptr, tail = nullptr;
-    if (chunks > 0)
-        TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, group, len, op.tmo, kSdmaChunk, &full, pull));
-    if (rest > 0) TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, group, len, op.tmo, rest, &tail, pull));
+    if (sp.chunks > 0)
+        TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, group, len, push.tmo, kSdmaChunk, &full, pull));
+    if (sp.rest > 0)
+        TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, group, len, push.tmo, sp.rest, &tail, pull));
     if (full || tail) HIPCK(launch_seqbase(me.scratch + kScrSeqBase, txs0, rxs0, 0, me.stream));
     double t0 = 0;
     TRY(stream_begin(me, check, iters, &t0));
-    // matched-receive order (Mailbox.posted), stream-ordered: post this
-    // call's receives, and a side that pushes first waits for the peer's
-    // post before its first copy into the peer's rx
-    if (iters > 0 && !test_knobs().no_posted) {
-        const u64 call = ++me.calls[peer_rank];
-        TRY(op.signal_abs(&peer.mb->posted[my_rank], call));
-        if (mode == MPX_MODE_NONBLOCKING || group == 1) TRY(op.wait_abs(&me.mb->posted[peer_rank], call));
-    }
-    if (check && mode == MPX_MODE_NONBLOCKING && !pull) {
-        TRY(op.nb_checked(iters, len, txs0, rxs0, slots));
-    } else {
-        for (int c = 0; c < chunks; ++c) HIPCK(hipGraphLaunch(full, me.stream));
-        if (tail) HIPCK(hipGraphLaunch(tail, me.stream));
-        int inflight = 0;
-        const int replayed = chunks * kSdmaChunk + rest;
-        for (int i = replayed; i < iters; ++i) TRY(op.step(mode, group, len, i, iters, txs0, rxs0, check, &inflight));
-        if (pull) {
-            // pulled: every receive is complete on this stream; the final
-            // Waitall's receives are counted (check mode), and a side that
-            // sent B-byte payloads waits for the peer's copies of its tx
-            if (mode == MPX_MODE_NONBLOCKING && check && inflight > 0)
-                HIPCK(launch_account(me.status, me.csum, iters - inflight, inflight, len, me.stream));
-            if (iters > 0 && (mode != MPX_MODE_UNIDIR || group == 1)) TRY(op.wait_pulled(txs0 + iters));
-        } else if (mode == MPX_MODE_NONBLOCKING && iters > 0 && (iters % kNbWindow) != 0) {
-            TRY(op.wait(rxs0 + iters));
+    int launches = 0;
+    auto enqueue = [&](auto op) -> int {
+        // matched-receive order (Mailbox.posted), stream-ordered: post this
+        // call's receives, and a side that pushes first waits for the peer's
+        // post before its first copy into the peer's rx
+        if (iters > 0 && !test_knobs().no_posted) {
+            const u64 call = ++me.calls[peer_rank];
+            TRY(op.signal(&peer.mb->posted[my_rank], nullptr, call));
+            if (mode == MPX_MODE_NONBLOCKING || group == 1) TRY(op.wait(&me.mb->posted[peer_rank], nullptr, call));
         }
-        // every receive of ping-pong / unidir is complete here; the device
-        // counts them and digests their checksums
-        if (check && iters > 0 && mode != MPX_MODE_NONBLOCKING)
-            HIPCK(launch_account(me.status, me.csum, 0, iters,
-                                 (mode == MPX_MODE_UNIDIR && group == 1) ? 1 : len, me.stream));
-    }
-    // graph replays count once each
-    TRY(stream_end(me, check, mode, iters, t0, op.launches + (chunks + (tail ? 1 : 0)),
-                   pull ? kProtoSdmaPull : kProtoSdma, t));
+        for (int k = 0; k < sp.chunks; ++k) HIPCK(hipGraphLaunch(full, me.stream));
+        if (tail) HIPCK(hipGraphLaunch(tail, me.stream));
+        const int replayed = sp.chunks * kSdmaChunk + sp.rest;
+        int inflight = replayed % kSdmaChunk;   // the window a replayed remainder leaves open
+        TRY(stream_loop(op, c, replayed, iters, &inflight));
+        TRY(stream_tail(op, c, inflight));
+        launches = op.launches + sp.chunks + (tail ? 1 : 0);   // graph replays count once each
+        return MPX_OK;
+    };
+    TRY(nbcheck ? enqueue(SdmaNbChecked{push, iters, slots}) : pull ? enqueue(SdmaPull{push}) : enqueue(push));
+    TRY(stream_end(me, check, mode, iters, t0, launches, pull ? kProtoSdmaPull : kProtoSdma, t));
     if (__atomic_load_n(&me.status->err, __ATOMIC_ACQUIRE)) {
         me.broken = true;
         return fail(MPX_ERR_TIMEOUT, "rank %d <- rank %d: SDMA-engine wait timed out (flag %llu, awaited %llu; "
@@ -469,72 +391,59 @@ int run_sdma(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int gro
 }
 
 // ---------------------------------------------------------------------------
-// engine: RCCL — ncclSend/ncclRecv on the rank's stream
+// engine: RCCL — ncclSend/ncclRecv on the rank's stream: 2 launches per
+// blocking iteration, 1 per non-blocking group
 // ---------------------------------------------------------------------------
+namespace {
+struct RcclOps : RankOps {
+    int peer_rank;
+    int send(long long len, int, bool, bool lost, bool) {
+        // test knob: the "lost" send carries rx (poison or stale bytes), not tx
+        const void* src = lost ? (const void*)me.rx : (const void*)me.tx;
+        const size_t n = (size_t)len;
+        NCCLCK(rccl_api().Send(src, n, ncclChar, peer_rank, me.comm, me.stream));
+        ++launches;
+        return MPX_OK;
+    }
+    int recv(long long len, int, bool, bool, bool) {
+        const size_t n = (size_t)len;
+        NCCLCK(rccl_api().Recv(me.rx, n, ncclChar, peer_rank, me.comm, me.stream));
+        ++launches;
+        return MPX_OK;
+    }
+    // Isend + Irecv of one iteration: one fused group (full duplex).  Check
+    // mode: the receive lands in rx and is checksummed (and poisoned) on this
+    // stream before the next group's receive can land — RCCL writes only this
+    // rank's own buffer, so no slots or credits are needed; the device counts
+    // the Waitall receives.
+    int nb_post(long long len, int, bool, bool lost) {
+        const void* src = lost ? (const void*)me.rx : (const void*)me.tx;
+        const size_t n = (size_t)len;
+        NCCLCK(rccl_api().GroupStart());
+        NCCLCK(rccl_api().Send(src, n, ncclChar, peer_rank, me.comm, me.stream));
+        NCCLCK(rccl_api().Recv(me.rx, n, ncclChar, peer_rank, me.comm, me.stream));
+        NCCLCK(rccl_api().GroupEnd());
+        ++launches;
+        return MPX_OK;
+    }
+    int nb_flush(int, int) { return MPX_OK; }   // stream order completes every receive
+    int drain(const StreamCall&, int) { return MPX_OK; }
+};
+}  // namespace
+
 int run_rccl(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int group, int iters, long long len,
              const mpx_xfer_opts* o, mpx_timing* t) {
     (void)peer;
-    (void)my_rank;
     if (!me.comm) return fail(MPX_ERR_STATE, "rank %d has no RCCL communicator (mpx_rccl_init_*)", my_rank);
     const int check = (o && o->check) ? 1 : 0;
-    const size_t n = (size_t)len;
-    const int skip = test_knobs().skip_push;
+    const StreamCall c{mode, group, len, iters, check != 0, nb_publish(), test_knobs().skip_push};
     double t0 = 0;
     TRY(stream_begin(me, check, iters, &t0));
-    int launches = 0, inflight = 0;
-    for (int i = 0; i < iters; ++i) {
-        // test knob: the "lost" send carries rx (poison or stale bytes), not tx
-        const void* src = skip == i + 1 ? (const void*)me.rx : (const void*)me.tx;
-        if (mode == MPX_MODE_PINGPONG) {
-            if (group == 1) {
-                NCCLCK(rccl_api().Send(src, n, ncclChar, peer_rank, me.comm, me.stream));
-                NCCLCK(rccl_api().Recv(me.rx, n, ncclChar, peer_rank, me.comm, me.stream));
-                if (check) TRY(stream_check(me, len, i, iters));
-            } else {
-                NCCLCK(rccl_api().Recv(me.rx, n, ncclChar, peer_rank, me.comm, me.stream));
-                if (check) TRY(stream_check(me, len, i, iters));
-                NCCLCK(rccl_api().Send(src, n, ncclChar, peer_rank, me.comm, me.stream));
-            }
-            launches += 2;
-        } else if (mode == MPX_MODE_UNIDIR) {
-            if (group == 1) {
-                NCCLCK(rccl_api().Send(src, n, ncclChar, peer_rank, me.comm, me.stream));
-                NCCLCK(rccl_api().Recv(me.rx, 1, ncclChar, peer_rank, me.comm, me.stream));
-                if (check) TRY(stream_check(me, 1, i, iters));
-            } else {
-                NCCLCK(rccl_api().Recv(me.rx, n, ncclChar, peer_rank, me.comm, me.stream));
-                if (check) TRY(stream_check(me, len, i, iters));
-                NCCLCK(rccl_api().Send(src, 1, ncclChar, peer_rank, me.comm, me.stream));
-            }
-            launches += 2;
-        } else {
-            // Isend + Irecv of one iteration: one fused group (full duplex).
-            // Check mode: the receive lands in rx and is checksummed (and
-            // poisoned) on this stream before the next group's receive can
-            // land — RCCL writes only this rank's own buffer, so no slots or
-            // credits are needed; the device counts the Waitall receives.
-            NCCLCK(rccl_api().GroupStart());
-            NCCLCK(rccl_api().Send(src, n, ncclChar, peer_rank, me.comm, me.stream));
-            NCCLCK(rccl_api().Recv(me.rx, n, ncclChar, peer_rank, me.comm, me.stream));
-            NCCLCK(rccl_api().GroupEnd());
-            launches += 1;
-            if (check) {
-                TRY(stream_check(me, len, i, iters));
-                if (inflight == kNbWindow - 1) {       // Waitall(255): iterations i-255 .. i-1
-                    HIPCK(launch_account(me.status, me.csum, i - inflight, inflight, len, me.stream));
-                    inflight = 0;
-                } else {
-                    ++inflight;
-                }
-            }
-        }
-    }
-    if (check && mode == MPX_MODE_NONBLOCKING && inflight > 0)
-        HIPCK(launch_account(me.status, me.csum, iters - inflight, inflight, len, me.stream));
-    if (check && mode != MPX_MODE_NONBLOCKING && iters > 0)
-        HIPCK(launch_account(me.status, me.csum, 0, iters, (mode == MPX_MODE_UNIDIR && group == 1) ? 1 : len,
-                             me.stream));
-    return stream_end(me, check, mode, iters, t0, launches, kProtoRccl, t);
+    RcclOps op{{me}, peer_rank};
+    int inflight = 0;
+    TRY(stream_loop(op, c, 0, iters, &inflight));
+    TRY(stream_tail(op, c, inflight));
+    return stream_end(me, check, mode, iters, t0, op.launches, kProtoRccl, t);
 }
 
 }  // namespace mpx
@@ -568,18 +477,15 @@ int rccl_link(Rank& me, int my_rank, int peer_rank) {
 int mpx_xfer_prepare(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, int iters, int buff_len,
                      const mpx_xfer_opts* opts) {
     if (!ctx) return fail(MPX_ERR_INVALID, "NULL argument");
-    if (mode < MPX_MODE_PINGPONG || mode > MPX_MODE_UNIDIR) return fail(MPX_ERR_INVALID, "mode %d", mode);
-    if (my_rank < 0 || my_rank >= ctx->nranks || peer_rank < 0 || peer_rank >= ctx->nranks)
-        return fail(MPX_ERR_INVALID, "ranks %d/%d", my_rank, peer_rank);
-    if (iters < 0 || buff_len < 0) return fail(MPX_ERR_INVALID, "iters %d, buff_len %d", iters, buff_len);
+    TRY(check_args(ctx, mode, nullptr, my_rank, peer_rank, iters, buff_len));
     Rank& me = ctx->r[my_rank];
     Rank& peer = ctx->r[peer_rank];
     if (!me.local) return fail(MPX_ERR_STATE, "rank %d is not attached in this process", my_rank);
     if (ctx->engine == MPX_ENGINE_RCCL) return rccl_link(me, my_rank, peer_rank);
     // the SDMA engine builds its graph-captured chunks per (mode, side, peer,
     // B): what run_sdma replays (not used in check mode)
-    if (ctx->engine != MPX_ENGINE_SDMA || (opts && opts->check) || !sdma_graphs_enabled() || iters < kSdmaGraphMin)
-        return MPX_OK;
+    const SdmaSplit sp = sdma_split(iters, opts && opts->check);
+    if (ctx->engine != MPX_ENGINE_SDMA || (sp.chunks == 0 && sp.rest == 0)) return MPX_OK;
     if (!peer.local && !peer.imported) return fail(MPX_ERR_STATE, "peer rank %d is unknown", peer_rank);
     const bool pull = pull_requested(opts);   // pulled chunks copy from the peer's tx: mapped first
     if (pull && buff_len > 0 && !peer.tx) TRY(ensure_peer_tx(ctx, peer, peer_rank));
@@ -587,11 +493,10 @@ int mpx_xfer_prepare(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer
     HIPCK(g.err);
     const u64 tmo = timeout_ticks(opts);
     hipGraphExec_t x = nullptr;
-    if (iters / kSdmaChunk > 0)
+    if (sp.chunks > 0)
         TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, my_group, buff_len, tmo, kSdmaChunk, &x, pull));
-    if (iters % kSdmaChunk >= kSdmaGraphMin)
-        TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, my_group, buff_len, tmo, iters % kSdmaChunk, &x,
-                             pull));
+    if (sp.rest > 0)
+        TRY(sdma_chunk_graph(me, peer, my_rank, peer_rank, mode, my_group, buff_len, tmo, sp.rest, &x, pull));
     return MPX_OK;
 }
 

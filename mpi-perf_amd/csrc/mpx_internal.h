@@ -11,6 +11,13 @@
 
 typedef unsigned long long u64;
 
+// returns a status other than MPX_OK to the caller
+#define TRY(expr)                     \
+    do {                              \
+        int s_ = (expr);              \
+        if (s_ != MPX_OK) return s_;  \
+    } while (0)
+
 namespace mpx {
 
 constexpr int kBlock = 256;              // threads per workgroup = 4 wave64

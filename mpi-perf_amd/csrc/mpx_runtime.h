@@ -61,12 +61,6 @@ struct RcclApi {
 };
 const RcclApi& rccl_api();
 
-#define TRY(expr)                     \
-    do {                              \
-        int s_ = (expr);              \
-        if (s_ != MPX_OK) return s_;  \
-    } while (0)
-
 inline double now_s() {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -258,6 +252,7 @@ bool pull_requested(const mpx_xfer_opts* o);
 int ensure_peer_tx(mpx_ctx* ctx, Rank& peer, int peer_rank);
 int ensure_peer_tx_locked(mpx_ctx* ctx, Rank& peer, int peer_rank);
 int check_rank_state(mpx_ctx* ctx, int my_rank, const void* tx, const void* rx, const int* peers, int npeers);
+int check_args(mpx_ctx* ctx, int mode, const int* my_group, int my_rank, int peer_rank, int iters, int buff_len);
 int check_call(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, int iters, void* tx, void* rx,
                int buff_len, const mpx_xfer_opts* opts);
 int check_verdict(Rank& me, int my_rank, int groups, int per, u64 n, const uint64_t* want, mpx_timing* t, int* bad,

@@ -994,20 +994,28 @@ int check_rank_state(mpx_ctx* ctx, int my_rank, const void* tx, const void* rx, 
     return MPX_OK;
 }
 
-// Argument checks and per-rank set-up shared by mpx_xfer_ex and mpx_xfer_arm.
-int check_call(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, int iters, void* tx, void* rx,
-               int buff_len, const mpx_xfer_opts* opts) {
+// The mode / rank / iters / length checks of a transfer call (check_call) and
+// of mpx_xfer_prepare, which passes no group: a prepare checks neither the
+// group nor the self-pair rule.
+int check_args(mpx_ctx* ctx, int mode, const int* my_group, int my_rank, int peer_rank, int iters, int buff_len) {
     if (mode < MPX_MODE_PINGPONG || mode > MPX_MODE_UNIDIR) return fail(MPX_ERR_INVALID, "mode %d", mode);
-    if (my_group != 0 && my_group != 1) return fail(MPX_ERR_INVALID, "group %d", my_group);
+    if (my_group && *my_group != 0 && *my_group != 1) return fail(MPX_ERR_INVALID, "group %d", *my_group);
     if (my_rank < 0 || my_rank >= ctx->nranks || peer_rank < 0 || peer_rank >= ctx->nranks)
         return fail(MPX_ERR_INVALID, "ranks %d/%d", my_rank, peer_rank);
     // a rank paired with itself: only the symmetric non-blocking loop (Isend +
     // Irecv to itself, MPI's self-send) — the one-kernel loopback every engine
     // can run on one GPU (RCCL refuses two ranks on one device), and the form
     // a profiler that serialises dispatches can trace
-    if (my_rank == peer_rank && mode != MPX_MODE_NONBLOCKING)
+    if (my_group && my_rank == peer_rank && mode != MPX_MODE_NONBLOCKING)
         return fail(MPX_ERR_INVALID, "rank %d paired with itself: only the non-blocking loop", my_rank);
     if (iters < 0 || buff_len < 0) return fail(MPX_ERR_INVALID, "iters %d, buff_len %d", iters, buff_len);
+    return MPX_OK;
+}
+
+// Argument checks and per-rank set-up shared by mpx_xfer_ex and mpx_xfer_arm.
+int check_call(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, int iters, void* tx, void* rx,
+               int buff_len, const mpx_xfer_opts* opts) {
+    TRY(check_args(ctx, mode, &my_group, my_rank, peer_rank, iters, buff_len));
     Rank& me = ctx->r[my_rank];
     Rank& peer = ctx->r[peer_rank];
     // RCCL addresses the peer by its communicator rank and maps nothing itself;
@@ -1076,7 +1084,7 @@ namespace {
 // After a completed loop: its algorithmic bytes and, in check mode, every
 // received payload's checksum against the peer's tx — in the non-blocking
 // loop too, where each receive has a slot of its own (k_xfer_nbcheck /
-// SdmaOps::nb_checked).
+// SdmaNbChecked).
 int finish_xfer(Rank& me, int mode, int my_group, int my_rank, int iters, int buff_len, const mpx_xfer_opts* opts,
                 mpx_timing* t) {
     t->bytes = (uint64_t)buff_len * (uint64_t)iters * (mode == MPX_MODE_UNIDIR ? 1u : 2u);

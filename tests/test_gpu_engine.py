@@ -12,6 +12,7 @@ import pytest
 
 import mpx
 import oracle_py as O
+import stream_launches as SL
 from pairs import Pairs
 
 pytestmark = pytest.mark.gpu
@@ -284,6 +285,29 @@ def test_sdma_graph_chunks_keep_sequence_state(mode):
             out, errs = P.run(mode, n, 5, check=True)
             assert not errs, (n, "checked run after chunks", errs)
             assert all(out[r].check_failures == 0 and out[r].check_iters == 5 for r in (0, 1))
+    finally:
+        P.close()
+
+
+@pytest.mark.parametrize("pull", [False, True])
+@pytest.mark.parametrize("mode", MODES)
+def test_stream_engine_launch_counts(mode, pull):
+    """What the SDMA engine enqueues for a call, counted: mpx_timing.launches
+    of both ranks against the literals of tests/stream_launches.py, pushed and
+    pulled, plainly enqueued, in check mode around one non-blocking window,
+    and graph-replayed; and the protocol the call reports."""
+    P = Pairs("sdma", 1, 4097, fill="seeded")
+    try:
+        for n in SL.SIZES:
+            for iters, check in SL.SHAPES:
+                out, errs = P.run(mode, n, iters, check=check, pull=pull)
+                assert not errs, (n, iters, errs)
+                for r in (0, 1):
+                    t = out[r]
+                    assert t.launches == SL.launches(pull, mode, P.group(r), n, iters, check), (n, iters, check, r)
+                    assert t.protocol == (8 if pull else 2), (n, iters, r)
+                    if check:
+                        assert t.check_iters == iters and t.check_failures == 0, (n, iters, r)
     finally:
         P.close()
 

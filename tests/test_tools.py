@@ -170,3 +170,48 @@ def test_link_counter_control_peer_cases_pick_the_formula(peer, per_byte, want):
     if want is None:
         assert f["reason"].startswith("one GPU" if peer == 0 else "no formula")
     assert r["cases"]["copy->peer_hbm_ipc"]["copy_checked_by_owner"] is True
+
+
+# ---- tools/stream_loop_check.cpp: the stream engines' loop on the CPU ---------
+def test_stream_loop_on_the_cpu(tmp_path):
+    """mpx_stream_loop.h compiled with plain g++ and run with a recording
+    operations object: its own checks (exact sequences per engine, window
+    arithmetic, publish schedule, capture equivalence) pass; the launches it
+    counts, plus the call's handshake and graph replays, are the literals the
+    GPU test holds the SDMA engine to (tests/stream_launches.py); and a checked
+    non-blocking call accounts for the receives the compiled reference's ranks
+    completed (tests/golden/ref_runs.json, the shim's recv_done per run)."""
+    import shutil
+
+    import oracle_py as O
+    import stream_launches as SL
+
+    if shutil.which("g++") is None:
+        pytest.skip("no C++ compiler")
+    exe = str(tmp_path / "stream_loop_check")
+    b = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                        "-I" + os.path.join(ROOT, "mpi-perf_amd", "csrc"),
+                        os.path.join(ROOT, "tools", "stream_loop_check.cpp"), "-o", exe],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-1500:]
+    p = subprocess.run([exe, "counts"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, (p.stdout[-400:], p.stderr[-1500:])
+    rows = [ln.split() for ln in p.stdout.splitlines()]
+    seen = set()
+    for _, pull, mode, group, n, iters, check, i0, count in ([r[0]] + [int(x) for x in r[1:]] for r in rows
+                                                             if r[0] == "launches"):
+        replays, covered = SL.replayed(iters, bool(check))
+        assert i0 == covered, (pull, mode, group, n, iters, check)
+        want = SL.launches(bool(pull), mode, group, n, iters, bool(check))
+        assert want == count + SL.handshake(mode, group, iters) + replays, (pull, mode, group, n, iters, check)
+        seen.add((pull, mode, group, n, iters, check))
+    assert len(seen) == 2 * 3 * 2 * len(SL.SIZES) * len(SL.SHAPES)     # every literal of the table
+    accounted = {(r[1], int(r[2])): int(r[3]) for r in rows if r[0] == "accounted"}
+    golden = {c["name"]: c for c in O.golden()["cases"]}
+    for iters, per_run in [(255, 255), (256, 255), (257, 256), (512, 510), (600, 598)]:
+        c = golden[f"nonblocking_window_i{iters}"]
+        runs = int(c["args"][c["args"].index("-r") + 1])
+        for rank in ("0", "1"):
+            assert c["shim"][rank]["recv_done"] == runs * per_run
+        for kind in ("pull", "nbcheck", "rccl"):
+            assert accounted[(kind, iters)] * runs == c["shim"]["0"]["recv_done"], (kind, iters)
