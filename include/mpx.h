@@ -112,7 +112,9 @@ typedef struct mpx_timing {
                                  7 = bulk payloads pulled by the receiver
                                  (MPX_XFER_PULL), 8 = the SDMA engine's
                                  pulled form, 9 = fan exchange (mpx_xfer_fan),
-                                 10 = lock-step LL fan exchange (MPX_FAN_LL)    */
+                                 10 = lock-step LL fan exchange (MPX_FAN_LL),
+                                 11 = host link, LL granules, 12 = host link,
+                                 bulk (mpx_xfer_hostlink, mpx_host_xfer)        */
     int32_t check_failures;   /* iterations whose payload checksum mismatched  */
     uint64_t check_iters;     /* iterations whose payload was checksummed      */
     /* receive accounting, as the reference's loop completes receives: every
@@ -212,6 +214,7 @@ int mpx_live_events(int *count);
    a call that failed before its launch leaves all four as they were.
    MPX_ERR_INVALID: my_rank is not a local rank of this context (an imported
    rank's counters live in its own process), or peer_rank is out of range.
+   A host endpoint (mpx_hostlink.h) is accepted as my_rank too: out[3] = 0.
    Call it between calls of my_rank, not while one runs. */
 int mpx_link_counters(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t out[4]);
 /* TEST ONLY: adds seq_by to out[0] and out[1] above, calls_by to out[2] and
@@ -490,6 +493,12 @@ int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
    MPX_FAN_LAT_RAW_MAX are declared, with their contract, in a header of their
    own, which is part of this one. */
 #include "mpx_fan_lat.h"
+
+/* ---- host link: the pair loops between a GPU rank and a CPU endpoint ------- */
+/* mpx_host_attach, mpx_host_buffers, mpx_xfer_hostlink, mpx_host_xfer,
+   mpx_host_checksum and mpx_hostlink_ll_max are declared, with their
+   contract, in a header of their own, which is part of this one. */
+#include "mpx_hostlink.h"
 
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of

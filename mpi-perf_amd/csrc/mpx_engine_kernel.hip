@@ -1,7 +1,7 @@
 // mpx_engine_kernel.hip — the kernel engine's host side: one lifecycle (take
 // the call's numbers, launch, complete) that the pair call (run_kernel), the
-// armed call (mpx_xfer_arm, start_armed, disarm) and the fan call
-// (mpx_xfer_fan) all go through.
+// armed call (mpx_xfer_arm, start_armed, disarm), the fan call (mpx_xfer_fan)
+// and the host-link call (run_hostlink_kernel) all go through.
 #include "mpx_runtime.h"
 
 #include <algorithm>
@@ -397,6 +397,32 @@ int run_kernel(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank, i
         return st;
     }
     return complete_pair(me, kc, t_call, t);
+}
+
+// A host-link call (mpx_xfer_hostlink; its arguments are built in
+// mpx_engine_hostlink.hip): the same three steps with k_xfer_hostlink.
+int run_hostlink_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, int grid, bool ll, double t_call,
+                        mpx_timing* t) {
+    const TestKnobs knobs = test_knobs();
+    Call c;
+    c.my_rank = my_rank;
+    c.iters = a.iters;
+    c.kernel = "host-link kernel";
+    c.fail_launch = knobs.fail_launch == my_rank;
+    c.nwg = ll ? 1 : a.nwg;
+    c.protocol = ll ? kProtoHostLL : kProtoHostBulk;
+    if (a.check) c.csum_words = (size_t)a.iters;
+    take_numbers(me, c, &host_rank, 1, knobs.no_posted, &a.call);
+    a.done_token = c.token;
+    const int st = launch_call(me, c, [&] { return launch_hostlink(a, grid, me.stream); });
+    if (st != MPX_OK) {
+        give_back(me, c);
+        return st;
+    }
+    return complete_call(me, c, &host_rank, 1, t_call, t, nullptr, [&](unsigned iteration) {
+        return fail(MPX_ERR_TIMEOUT, "rank %d <- host endpoint %d: device wait timed out at iteration %u (mode %d, %lld B)",
+                    my_rank, host_rank, iteration, a.mode, a.len);
+    });
 }
 
 // Start the armed call: one host store; the kernel has been waiting for it.

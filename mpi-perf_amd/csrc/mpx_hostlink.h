@@ -1,0 +1,269 @@
+// mpx_hostlink.h — the host link's shared memory layout and the CPU endpoint's
+// side of the transfer loops (include/mpx_hostlink.h: mpx_host_xfer).  Plain
+// C++: no HIP include, every shared word is a uint64_t read and written
+// through the __atomic_* builtins, so the file builds with g++ alone
+// (tools/hostlink_host_check.cpp runs it under the host sanitizers with a
+// second CPU thread in the GPU's place).
+//
+// A host endpoint cannot write device memory, so every word and byte that
+// crosses the link lives in pinned host memory and the GPU does all the
+// moving (DESIGN.md §5 "Host link"):
+//   GPU -> CPU  LL granules into in.ll, or a bulk push into the endpoint's rx
+//               (payload stores, per-workgroup drain, then in.flag[w]);
+//   CPU -> GPU  LL granules into out.ll, which the GPU's workgroup 0 polls
+//               across the link, or "tx holds message k" in out.ready, after
+//               which the GPU's workgroups load their chunks of the
+//               endpoint's tx themselves and answer with in.credit[w].
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+#include <time.h>
+
+#if defined(__x86_64__) || defined(__i386__)
+#include <immintrin.h>
+#endif
+
+namespace mpx {
+namespace hostlink {
+
+// the library's limits (mpx_internal.h; mpx_engine_hostlink.hip asserts them equal)
+constexpr int kRanks = 64;          // MPX_MAX_RANKS
+constexpr int kWG = 256;            // kMaxPushWG: flag / credit words per link
+constexpr int kLLBytes = 8192;      // kLLMaxBytes: the LL landing row
+constexpr int kGranules = kLLBytes / 4;
+constexpr int kMinChunk = 1024;     // kMinPushChunk
+// The LL threshold: the largest size of the probe's sweep (256 B ... 8 KiB,
+// powers of two) at which LL granules were not slower than the bulk form —
+// across PCIe a granule poll is a link round trip, and from 512 B on the bulk
+// form's one flag per workgroup wins (profiles/hostlink.jsonl)
+constexpr int kDefaultLL = 256;
+// The default width's cap: unidir at 4 MiB read best at 4-32 workgroups in
+// both directions and lost 11-22 % at the pair rule's 128 (same profile)
+constexpr int kDefaultMaxWG = 16;
+
+// One direction of a host endpoint's mailbox.  It has the layout of the
+// device mailbox (Mailbox, mpx_internal.h), so the kernels' pushes, polls and
+// pulls address it as they address a GPU peer's.  Rows are indexed by the GPU
+// peer's rank.
+struct HostBox {
+    uint64_t flag[kRanks][kWG];       // sequence number of the last bulk push of workgroup w
+    uint64_t ll[kRanks][kGranules];   // LL granules {tag:32 | payload:32}
+    uint64_t credit[kRanks][kWG];     // last pulled push whose chunk w is done with
+    uint64_t posted[kRanks];          // "receives posted": the link's call number
+    uint64_t ready[kRanks];           // "tx holds message k"
+};
+// in : written by the GPU, read by the CPU   — flag, ll, credit, posted
+// out: written by the CPU, polled by the GPU — ll (the ll_out row), ready, posted
+struct HostMailbox {
+    HostBox in;
+    HostBox out;
+};
+
+inline void cpu_pause() {
+#if defined(__x86_64__) || defined(__i386__)
+    _mm_pause();
+#endif
+}
+inline double now_s() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (double)ts.tv_sec + (double)ts.tv_nsec * 1e-9;
+}
+inline uint64_t ld_acq(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
+inline void st_rel(uint64_t* p, uint64_t v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
+
+inline uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+// mpx_checksum's value (oracle_checksum): the sum over the
+// zero-padded little-endian 64-bit words w_k of mix64(w_k + (k + 1) * golden),
+// finished with ^ mix64(n).  Any alignment.
+inline uint64_t checksum(const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    uint64_t sum = 0;
+    size_t k = 0;
+    for (; 8 * k + 8 <= n; ++k) {
+        uint64_t w;
+        memcpy(&w, b + 8 * k, 8);
+        sum += mix64(w + (k + 1) * 0x9E3779B97F4A7C15ull);
+    }
+    if (8 * k < n) {
+        uint64_t w = 0;
+        memcpy(&w, b + 8 * k, n - 8 * k);
+        sum += mix64(w + (k + 1) * 0x9E3779B97F4A7C15ull);
+    }
+    return sum ^ mix64((uint64_t)n);
+}
+// The kernels' poison of iteration `iter`, form by form (Loop::check): an LL
+// message gets the pattern's low byte in every byte; a bulk message the 64-bit
+// pattern over its whole 16-byte units (Loop::sum_chunk: chunks are multiples
+// of 16 bytes, so the units are the message's) and the low byte over the
+// tail.  Any value that differs from the payload would serve; it is the same
+// one so that a poisoned rx reads alike whichever side received.
+inline void poison(unsigned char* p, size_t n, int iter, bool ll) {
+    const uint64_t w = 0x5a5a5a5a5a5a5a5aull ^ (uint64_t)iter;
+    const size_t units = ll ? 0 : n & ~(size_t)15;   // bytes in whole 16-byte units
+    for (size_t o = 0; o < units; o += 8) memcpy(p + o, &w, 8);
+    for (size_t o = units; o < n; ++o) p[o] = (unsigned char)w;
+}
+
+// ll_tag (mpx_internal.h): never 0, distinct for push numbers < 2^31 apart
+inline uint32_t ll_tag(uint64_t seq) { return (uint32_t)(seq & 0x7fffffffull) | 0x80000000u; }
+// 16-byte units of an LL message: the kernels store and poll whole units, so
+// both granules of the last unit carry the tag; a 0-byte message is one unit
+inline int ll_units(long long n) {
+    const int ng = n > 0 ? (int)((n + 3) >> 2) : 1;
+    return (ng + 1) >> 1;
+}
+// link_nwg's narrowing (mpx_internal.h): at least kMinChunk bytes per workgroup
+inline int narrow_nwg(int w, long long len) {
+    const long long most = (len + kMinChunk - 1) / kMinChunk;
+    const long long n = w < most ? w : most;
+    return n < 1 ? 1 : (int)n;
+}
+
+// One call of the CPU endpoint.
+struct Call {
+    HostMailbox* mb = nullptr;
+    const unsigned char* tx = nullptr;
+    unsigned char* rx = nullptr;
+    int gpu = 0;               // the GPU peer's rank: the mailbox row
+    int mode = 0, group = 0;   // enum mpx_mode (0 ping-pong, 2 unidir); 1 = sends first
+    int iters = 0;
+    long long len = 0;
+    int nwg = 1;               // the link's width (both ends compute it alike)
+    int ll_max = kDefaultLL;   // messages <= ll_max go as LL granules
+    int check = 0;
+    uint64_t expect = 0, expect_ack = 0;
+    uint64_t tx_seq0 = 0, rx_seq0 = 0;   // the link's push numbers before the call
+    uint64_t call = 0;         // the link's call number (posted)
+    double timeout_s = 10.0;   // per wait, CLOCK_MONOTONIC
+    int skip_push = 0;         // test knob: 1 + the iteration whose payload is lost
+};
+struct Result {
+    uint64_t recv_done = 0, recv_digest = 0, check_iters = 0;
+    int check_failures = 0;
+    int timed_out = 0;         // 1: a wait ran past its deadline,
+    int where = 0;             //    at this iteration
+};
+
+namespace detail {
+
+struct Waiter {
+    double timeout_s;
+    // spins until pred() holds; false once the deadline has passed
+    template <class Pred>
+    bool until(Pred pred) const {
+        const double t0 = now_s();
+        for (unsigned spins = 1;; ++spins) {
+            if (pred()) return true;
+            if ((spins & 255) == 0 && now_s() - t0 > timeout_s) return pred();
+            cpu_pause();
+        }
+    }
+};
+
+// CPU -> GPU, LL: granules into out.ll; data and tag share their 8 bytes, so
+// each granule is one store and the GPU's poll that sees the tag holds the data
+inline void send_ll(const Call& c, long long n, uint64_t seq, bool lose) {
+    uint64_t* row = c.mb->out.ll[c.gpu];
+    const uint64_t tag = (uint64_t)ll_tag(seq) << 32;
+    const int ng = 2 * ll_units(n);
+    for (int g = 0; g < ng; ++g) {
+        uint32_t w = 0;
+        const long long off = 4ll * g;
+        if (!lose && off < n) memcpy(&w, c.tx + off, (size_t)(n - off < 4 ? n - off : 4));
+        __atomic_store_n(&row[g], tag | w, __ATOMIC_RELEASE);
+    }
+}
+// GPU -> CPU, LL: every granule's tag, then the unpack into rx[0:n)
+inline bool recv_ll(const Call& c, const Waiter& w, long long n, uint64_t seq) {
+    const uint64_t* row = c.mb->in.ll[c.gpu];
+    const uint32_t tag = ll_tag(seq);
+    const int ng = 2 * ll_units(n);
+    for (int g = 0; g < ng; ++g) {
+        uint64_t v = 0;
+        if (!w.until([&] { return (uint32_t)((v = ld_acq(&row[g])) >> 32) == tag; })) return false;
+        const long long off = 4ll * g;
+        if (off < n) {
+            const uint32_t d = (uint32_t)v;
+            memcpy(c.rx + off, &d, (size_t)(n - off < 4 ? n - off : 4));
+        }
+    }
+    return true;
+}
+// GPU -> CPU, bulk: the GPU's workgroups stored their chunks into rx and
+// drained before their flags
+inline bool recv_bulk(const Call& c, const Waiter& w, uint64_t seq) {
+    const uint64_t* f = c.mb->in.flag[c.gpu];
+    for (int k = 0; k < c.nwg; ++k)
+        if (!w.until([&] { return ld_acq(&f[k]) >= seq; })) return false;
+    return true;
+}
+// CPU -> GPU, bulk: tx holds the message; the GPU pulls it and credits every chunk
+inline bool send_bulk(const Call& c, const Waiter& w, uint64_t seq) {
+    st_rel(&c.mb->out.ready[c.gpu], seq);
+    const uint64_t* cr = c.mb->in.credit[c.gpu];
+    for (int k = 0; k < c.nwg; ++k)
+        if (!w.until([&] { return ld_acq(&cr[k]) >= seq; })) return false;
+    return true;
+}
+
+}  // namespace detail
+
+// The endpoint's side of the reference's ping-pong (mpi_perf.c:66-83) or
+// unidirectional (:127-145) loop on the calling thread.  Returns 0, or 1 after
+// a wait that ran out (r->timed_out, r->where).
+inline int run(const Call& c, Result* r) {
+    using namespace detail;
+    *r = Result{};
+    const Waiter w{c.timeout_s};
+    const bool unidir = c.mode == 2;
+    const long long send_len = (unidir && c.group == 0) ? 1 : c.len;
+    const long long recv_len = (unidir && c.group == 1) ? 1 : c.len;
+    const uint64_t want = (unidir && c.group == 1) ? c.expect_ack : c.expect;
+    uint64_t txs = c.tx_seq0, rxs = c.rx_seq0;
+    // this call's receives are posted; a side that sends first waits for the peer's
+    st_rel(&c.mb->out.posted[c.gpu], c.call);
+    if (c.iters > 0 && c.group == 1 && !w.until([&] { return ld_acq(&c.mb->in.posted[c.gpu]) >= c.call; })) {
+        r->timed_out = 1;
+        return 1;
+    }
+    auto send = [&](int i) {
+        ++txs;
+        if (send_len <= c.ll_max) {
+            send_ll(c, send_len, txs, !(unidir && c.group == 0) && c.skip_push == i + 1);   // (never an ack)
+            return true;
+        }
+        return send_bulk(c, w, txs);   // (a lost bulk payload is the puller's to lose)
+    };
+    auto recv = [&](int i) {
+        ++rxs;
+        if (!(recv_len <= c.ll_max ? recv_ll(c, w, recv_len, rxs) : recv_bulk(c, w, rxs))) return false;
+        ++r->recv_done;
+        if (c.check) {
+            const uint64_t got = checksum(c.rx, (size_t)recv_len);
+            r->recv_digest += got;
+            ++r->check_iters;
+            if (got != want) ++r->check_failures;
+            if (i + 1 != c.iters) poison(c.rx, (size_t)recv_len, i, recv_len <= c.ll_max);   // the last payload stays
+        }
+        return true;
+    };
+    for (int i = 0; i < c.iters; ++i) {
+        const bool ok = c.group == 1 ? (send(i) && recv(i)) : (recv(i) && send(i));
+        if (!ok) {
+            r->timed_out = 1;
+            r->where = i;
+            return 1;
+        }
+    }
+    return 0;
+}
+
+}  // namespace hostlink
+}  // namespace mpx

@@ -30,7 +30,8 @@ constexpr int kStageMaxBytes = 60 << 10; // LDS-staged tx chunk per workgroup, m
 
 // Protocol ids reported in mpx_timing.protocol
 enum Proto { kProtoLL = 0, kProtoBulk = 1, kProtoSdma = 2, kProtoRccl = 3, kProtoCopy = 4, kProtoCopySteps = 5,
-             kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8, kProtoFan = 9, kProtoFanLL = 10 };
+             kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8, kProtoFan = 9, kProtoFanLL = 10, kProtoHostLL = 11,
+             kProtoHostBulk = 12 };
 
 // One rank's receive mailbox, in that rank's HBM (uncached / fine-grained so a
 // poll sees stores that arrive over xGMI).  Written ONLY by the peers, polled
@@ -135,9 +136,12 @@ constexpr u64 kGoCancel = 1ull << 63;
 //   [8] armed call: workgroup 0's go verdict for the others (1 go, 2 cancel),
 //       reset with [0..3]
 //   [9] armed call: workgroups other than 0 waiting for go, reset with [0..3]
+//   [10] host link: receives of this call workgroup 0 has seen arrive in host
+//        memory, republished for the other workgroups; reset by the call's end
+//   [11] host link: 1 once workgroup 0 has seen the endpoint's post; likewise
 constexpr int kScratchWords = 16;
 constexpr int kScrBar = 0, kScrAbort = 1, kScrFin = 2, kScrLanded = 3, kScrSeqBase = 4, kScrLink = 6, kScrGo = 8,
-              kScrReady = 9;
+              kScrReady = 9, kScrHostSeen = 10, kScrHostPosted = 11;
 
 // Non-blocking check mode ("ring"): receive j of a call with `iters`
 // iterations lands in slot (iters-1-j) mod S of the receiver, where slot 0 is
@@ -368,6 +372,9 @@ inline int fan_build_map(FanTable* tab, int nlinks, const int* nwg, int iters) {
 hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s);
 hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s);   // grid = a.f.nlinks
 hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s);
+// the host link's kernel (k_xfer_hostlink): ping-pong and unidir only; my_mb /
+// peer_mb are the endpoint's out / in boxes, my_slot = peer_slot = this rank
+hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s);
 hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out);
 // all `iters` copies in one launch with a grid barrier between steps; *bar
 // must be 0 at launch

@@ -11,6 +11,9 @@
 //   k_xfer_fan_ll  the same with MPX_FAN_LL: per link a lock-step exchange of
 //               LL granules, one workgroup per link (<CHECK, LAT>: LAT is the
 //               form traced per link, mpx_fan_lat_*)
+//   k_xfer_hostlink  a GPU rank's side of the ping-pong / unidir loop with a
+//               CPU endpoint across PCIe (mpx_xfer_hostlink): the same pushes,
+//               and bulk receives pulled from the endpoint's pinned tx
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -1626,6 +1629,122 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull_lat(XferArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// k_xfer_hostlink: a GPU rank's side of the ping-pong or unidir loop with a
+// CPU endpoint (mpx_xfer_hostlink; the endpoint's side is mpx_hostlink.h's
+// run()).  The endpoint cannot write device memory, so every shared word and
+// byte is in pinned host memory and this kernel does all the moving:
+//   a.peer_mb  the endpoint's `in` box   (this rank writes: flag, ll, credit, posted)
+//   a.my_mb    the endpoint's `out` box  (this rank polls across the link: ll, ready, posted)
+//   a.peer_rx / a.peer_tx  the endpoint's rx / tx;  a.my_slot = a.peer_slot = this rank
+// Both boxes have the device mailbox's layout, so the sends are the pair
+// loops' own (Loop::push_ll, push_bulk: sc0 sc1 payload stores, every wave's
+// drain, then the flag) and so are the receives' bodies (Loop::wait_ll's
+// granule poll and unpack; Loop::pull_recv's chunk loads from the endpoint's
+// tx, check, credit).  What is new is who reads host memory while waiting:
+// only workgroup 0.  It polls the endpoint's word (posted, ready, or the LL
+// row) and republishes what it saw in a device scratch word (kScrHostPosted;
+// kScrHostSeen = receives of this call seen so far), which the other
+// workgroups poll at agent scope — as wait_go hands the host's go word on in
+// kScrGo — so that up to 255 pollers of one host line do not share the link
+// with the payload loads (a supposition, not a measurement: DESIGN.md §5).
+// Grid: 1 when both directions are LL, else a.nwg; co-resident (4 per CU).
+// ---------------------------------------------------------------------------
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
+    static_assert(MODE == MPX_MODE_PINGPONG || MODE == MPX_MODE_UNIDIR, "the blocking loops only");
+    // statics of 48 bytes: the dynamic region (the staged tx chunk) stays 16-byte aligned
+    __shared__ __attribute__((aligned(16))) u64 s_w[6];   // block_sum's four, s_seen, s_abort
+    extern __shared__ v4u s_tx[];
+    int* s_abort = reinterpret_cast<int*>(&s_w[5]);
+    if (threadIdx.x == 0) {
+        *s_abort = 0;
+        s_w[4] = 0;
+    }
+    __syncthreads();
+    Loop<MODE> L{a, s_abort, s_w, s_tx, {}, &s_w[4]};
+    L.stamp(kTsEntry);
+    const long long n = a.len;
+    constexpr bool sends_n = MODE != MPX_MODE_UNIDIR || GROUP == 1;   // else the 1-byte ack
+    constexpr bool recvs_n = MODE != MPX_MODE_UNIDIR || GROUP == 0;
+    const long long send_len = sends_n ? n : 1, recv_len = recvs_n ? n : 1;
+    const bool ll_send = L.is_ll(send_len), ll_recv = L.is_ll(recv_len);
+    const bool wg0 = blockIdx.x == 0;
+    if (wg0 && ll_send) L.preload_ll(send_len);
+    u64 txs = a.tx_seq0, rxs = a.rx_seq0, done = 0;
+    // workgroup 0 saw it in host memory: tell the others; they wait for that
+    auto relay = [&](int word, u64 v) {
+        if (threadIdx.x == 0 && gridDim.x > 1)
+            __hip_atomic_store(&a.gbar[word], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    L.post_receives();
+    bool ok = true;
+    if (GROUP == 1 && a.iters > 0) {
+        // this side pushes first: the endpoint's receives of this call are posted
+        if (wg0) {
+            ok = L.template poll_ge<true>(&a.my_mb->posted[a.peer_slot], a.call, 0);
+            if (ok) relay(kScrHostPosted, 1);
+        } else {
+            ok = L.template poll_ge<false>(&a.gbar[kScrHostPosted], 1, 0);
+        }
+        L.stamp(kTsPosted);
+    }
+    auto send = [&](int i) {
+        ++txs;
+        const bool lose = sends_n && a.skip_push == i + 1;   // test knob: a B-byte payload, never an ack
+        if (ll_send) {
+            // a side that received a bulk payload answers once every chunk is in
+            if (!ll_recv && wg0 && !L.template poll_ge<false>(&a.gbar[kScrLanded], (u64)a.nwg * (u64)(i + 1), i))
+                return false;
+            if (!lose) L.push_ll(send_len, txs);
+            else L.push_ll_tags_only(send_len, txs);
+        } else {
+            L.push_bulk(send_len, txs, true, nullptr, lose);
+        }
+        return true;
+    };
+    auto recv = [&](int i) {
+        ++rxs;
+        if (ll_recv) {
+            // the granules are in the endpoint's out row: workgroup 0 polls them across the link
+            if (wg0) {
+                if (!L.wait_ll(recv_len, rxs, i)) return false;
+                relay(kScrHostSeen, (u64)(i + 1));
+                if (a.check) L.check(recv_len, i);
+            } else if (!L.template poll_ge<false>(&a.gbar[kScrHostSeen], (u64)(i + 1), i)) {
+                return false;
+            }
+        } else {
+            // "tx holds message rxs": workgroup 0 reads the word, every workgroup pulls its chunk
+            if (wg0) {
+                if (!L.template poll_ge<true>(&a.my_mb->ready[a.peer_slot], rxs, i)) return false;
+                relay(kScrHostSeen, (u64)(i + 1));
+            } else if (!L.template poll_ge<false>(&a.gbar[kScrHostSeen], (u64)(i + 1), i)) {
+                return false;
+            }
+            if (threadIdx.x == 0) s_w[4] = rxs;          // (pull_recv's own wait finds the word seen)
+            __syncthreads();
+            if (!L.pull_recv(recv_len, rxs, i)) return false;
+        }
+        ++done;
+        return true;
+    };
+    for (int i = 0; ok && i < a.iters; ++i) {
+        if constexpr (GROUP == 1) ok = send(i) && recv(i);   // mpi_perf.c:72-75, 135-137
+        else ok = recv(i) && send(i);                        // mpi_perf.c:79-80, 141-142
+        if (i == 0) L.stamp(kTsFirst);
+    }
+    L.stamp(kTsLoop);
+    if (L.last_to_finish()) {
+        L.account(done, recv_len);
+        if (threadIdx.x == 0) {   // every other workgroup is done with the relay words
+            __hip_atomic_store(&a.gbar[kScrHostSeen], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&a.gbar[kScrHostPosted], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        L.finish_last();
+    }
+}
+
+// ---------------------------------------------------------------------------
 // k_xfer_fan: one rank's side of a fan exchange (mpx_xfer_fan) — a block to
 // and from each of several peers in ONE launch.  The grid is the sum of the
 // links' widths; workgroup (k, w) (FanTable.map) owns chunk w of link k and
@@ -1995,6 +2114,24 @@ hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), (unsigned)a.stage, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s) {
+    // the kernel indexes flag / credit words by workgroup and LL granules by length
+    if (grid < 1 || grid > kMaxPushWG || a.nwg < 1 || a.nwg > kMaxPushWG || (grid != 1 && grid != a.nwg) ||
+        a.ll_max < 0 || a.ll_max > kLLMaxBytes || a.len < 0 || a.stage < 0 || a.stage > kStageMaxBytes)
+        return hipErrorInvalidValue;
+    (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
+    void (*k)(XferArgs) = nullptr;
+    switch (a.mode) {
+        case MPX_MODE_PINGPONG:
+            k = a.group ? k_xfer_hostlink<MPX_MODE_PINGPONG, 1> : k_xfer_hostlink<MPX_MODE_PINGPONG, 0>;
+            break;
+        case MPX_MODE_UNIDIR: k = a.group ? k_xfer_hostlink<MPX_MODE_UNIDIR, 1> : k_xfer_hostlink<MPX_MODE_UNIDIR, 0>; break;
+        default: return hipErrorInvalidValue;
+    }
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), (unsigned)a.stage, s, a);
     return hipGetLastError();
 }
 

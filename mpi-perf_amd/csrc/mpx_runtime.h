@@ -2,8 +2,9 @@
 // reporting, the RAII holders, Rank and mpx_ctx, and the helpers more than one
 // part calls.  The parts: mpx_runtime.hip (contexts, buffers, registration,
 // copy, latency recorder, the C-ABI), mpx_engine_kernel.hip (the kernel
-// engine's call lifecycle: pair, armed and fan calls) and
-// mpx_engine_stream.hip (the SDMA and RCCL engines).  Nothing here is
+// engine's call lifecycle: pair, armed, fan and host-link calls),
+// mpx_engine_hostlink.hip (host endpoints and both sides of a host-link call)
+// and mpx_engine_stream.hip (the SDMA and RCCL engines).  Nothing here is
 // exported from libmpx.so.
 #pragma once
 
@@ -150,6 +151,14 @@ struct Rank {
     bool local = false;
     bool imported = false;
     bool broken = false;           // a transfer timed out: link state unknown
+    // a host endpoint (mpx_host_attach): neither local nor imported.  tx, rx and
+    // len are its pinned host buffers (CPU pointers); tx_seq / rx_seq / calls
+    // count as a local rank's and are touched only by mpx_host_xfer's thread
+    bool host = false;
+    void* host_mb = nullptr;       // its hostlink::HostMailbox, as the CPU addresses it
+    unsigned char* host_tx_dev = nullptr;   // tx, rx and the mailbox as the GPUs address them
+    unsigned char* host_rx_dev = nullptr;
+    void* host_mb_dev = nullptr;
     int dev = -1;
     char bus_id[32] = {0};
     unsigned char* tx = nullptr;   // local tx, or the imported rank's tx mapped here (pull mode:
@@ -264,6 +273,14 @@ int run_kernel(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank, i
 int start_armed(Rank& me, int my_rank, int peer_rank, int mode, int group, int iters, long long len,
                 const mpx_xfer_opts* o, double t_call, mpx_timing* t);
 int disarm(Rank& me);
+// a host-link call's kernel through the one call lifecycle: takes the call's
+// numbers on the link to host_rank (a.call, a.done_token), launches
+// k_xfer_hostlink and completes the call as a pair call's
+int run_hostlink_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, int grid, bool ll, double t_call,
+                        mpx_timing* t);
+
+// ---- mpx_engine_hostlink.hip: the host link ----------------------------------
+void free_host_endpoint(Rank& rk);   // mpx_finalize: a host endpoint's pinned memory
 
 // ---- mpx_engine_stream.hip: the SDMA and RCCL engines ------------------------
 int run_sdma(Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int group, int iters, long long len,

@@ -602,6 +602,7 @@ int mpx_finalize(mpx_ctx* ctx) {
     (void)hipGetLastError();
     for (int i = 0; i < MPX_MAX_RANKS; ++i) {
         Rank& rk = ctx->r[i];
+        if (rk.host) free_host_endpoint(rk);
         if (!rk.local) continue;
         DeviceGuard g(rk.dev);
         free_rank_memory(rk);
@@ -876,7 +877,8 @@ int mpx_rank_attach(mpx_ctx* ctx, int rank, int dev, void* tx, void* rx, size_t 
     TRY(check_dev(dev));
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (ctx->r[rank].local || ctx->r[rank].imported) return fail(MPX_ERR_STATE, "rank %d already registered", rank);
+        if (ctx->r[rank].local || ctx->r[rank].imported || ctx->r[rank].host)
+            return fail(MPX_ERR_STATE, "rank %d already registered", rank);
         auto it = ctx->allocs.find(reinterpret_cast<uintptr_t>(rx));
         if (it == ctx->allocs.end() || it->second.dev != dev || it->second.bytes < len)
             return fail(MPX_ERR_INVALID, "rx must be an mpx_alloc base on device %d of >= %zu bytes", dev, len);
@@ -943,7 +945,8 @@ int mpx_rank_import(mpx_ctx* ctx, int rank, const void* desc) {
     if (memcmp(d.magic, "MPXRANK2", 8) != 0 || d.abi != MPX_ABI_VERSION || d.rank != rank)
         return fail(MPX_ERR_INVALID, "descriptor is not an mpx rank %d descriptor", rank);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->r[rank].local || ctx->r[rank].imported) return fail(MPX_ERR_STATE, "rank %d already registered", rank);
+    if (ctx->r[rank].local || ctx->r[rank].imported || ctx->r[rank].host)
+        return fail(MPX_ERR_STATE, "rank %d already registered", rank);
     if (ctx->import_dev < 0) return fail(MPX_ERR_STATE, "attach a local rank before importing remote ranks");
     if (d.pid == (int64_t)getpid()) return fail(MPX_ERR_INVALID, "rank %d belongs to this process: attach it instead", rank);
     DeviceGuard g(ctx->import_dev);
@@ -1175,14 +1178,15 @@ int mpx_live_events(int* count) {
 
 int mpx_link_counters(mpx_ctx* ctx, int my_rank, int peer_rank, uint64_t out[4]) {
     if (!ctx || !out) return fail(MPX_ERR_INVALID, "NULL argument");
-    if (my_rank < 0 || my_rank >= ctx->nranks || !ctx->r[my_rank].local)
+    // (either end of a host link: a host endpoint counts its links as a local rank does)
+    if (my_rank < 0 || my_rank >= ctx->nranks || !(ctx->r[my_rank].local || ctx->r[my_rank].host))
         return fail(MPX_ERR_INVALID, "rank %d is not a local rank", my_rank);
     if (peer_rank < 0 || peer_rank >= ctx->nranks) return fail(MPX_ERR_INVALID, "peer rank %d", peer_rank);
     const Rank& me = ctx->r[my_rank];
     out[0] = me.tx_seq[peer_rank];
     out[1] = me.rx_seq[peer_rank];
     out[2] = me.calls[peer_rank];
-    out[3] = me.token;
+    out[3] = me.host ? 0 : me.token;
     return MPX_OK;
 }
 

@@ -72,7 +72,9 @@ void mpxh_print_usage(FILE *f)
 		    -L <raw-cap: record every iteration's latency, lat-*.csv (kernel engine, not -x 1)>\n\
 		    -m <1: every run is one fan exchange, each rank with all others at once (kernel engine)>\n\
 		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n\
-		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n");
+		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n\
+		    -H <1|2: each of the -w ranks is a GPU rank paired with a CPU endpoint across the host link;>\n\
+		       <1: the GPU rank sends first (-u 1: device to host), 2: the endpoint does (kernel engine, threads)>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -81,7 +83,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -115,6 +117,10 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
             o->arm_set = 1;
             break;
         case 'm': o->fan = atoi(optarg); break;
+        case 'H':
+            if (strcmp(optarg, "1") && strcmp(optarg, "2")) return MPXH_PARSE_BAD_VALUE;
+            o->hostlink = atoi(optarg);
+            break;
         case 'L': {
             char *end = NULL;
             const long v = strtol(optarg, &end, 10);
@@ -199,10 +205,60 @@ static int validate_fan(const mpxh_options *o, int world, FILE *err)
     return 0;
 }
 
+/* -H (a host-link run): pairs of a GPU rank and a CPU endpoint in one
+   process, the blocking loops of the kernel engine, never armed or traced */
+static int validate_hostlink(const mpxh_options *o, int world, FILE *err)
+{
+    const int h = o->hostlink;
+    if (o->nonblocking) {
+        fprintf(err, "invalid -H %d with -x 1: the host link runs the ping-pong and unidir loops only\n", h);
+        return 1;
+    }
+    if (o->all_pairs) {
+        fprintf(err, "invalid -H %d with -a 1: every GPU rank is paired with a host endpoint of its own\n", h);
+        return 1;
+    }
+    if (o->fan) {
+        fprintf(err, "invalid -H %d with -m %d: a fan run has no host endpoints\n", h, o->fan);
+        return 1;
+    }
+    if (o->arm_set && o->arm) {
+        fprintf(err, "invalid -H %d with -A 1: a host-link call cannot be armed ahead of the barrier\n", h);
+        return 1;
+    }
+    if (o->lat_cap >= 0) {
+        fprintf(err, "invalid -H %d with -L %d: host-link calls are never traced by the latency recorder\n", h, o->lat_cap);
+        return 1;
+    }
+    if (o->use_dotnet) {
+        fprintf(err, "invalid -H %d with -d 1: the .NET launcher lines describe pairs of ranks\n", h);
+        return 1;
+    }
+    if (o->engine != 0) {
+        fprintf(err, "invalid -H %d with -e sdma|rccl: the host link runs on the kernel engine only\n", h);
+        return 1;
+    }
+    if (o->procs) {
+        fprintf(err, "invalid -H %d with one process per rank: a host endpoint lives in its GPU rank's process (threads mode)\n",
+                h);
+        return 1;
+    }
+    if (world > MPXH_HOSTLINK_MAX_WORLD) {
+        fprintf(err, "invalid -H %d with -w %d: rank r's endpoint is rank world + r, so at most %d ranks\n", h, world,
+                MPXH_HOSTLINK_MAX_WORLD);
+        return 1;
+    }
+    return 0;
+}
+
 /* mpi_perf.c:399-403; first the rules of the new flags that need two of
-   them: -L traces the kernel engine's blocking loops only, -m 1 (above) */
+   them: -L traces the kernel engine's blocking loops only, -m 1 and -H (above) */
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
+    if (o->hostlink) {
+        if (validate_hostlink(o, world, err)) return 1;
+        world *= 2; /* the job: the GPU ranks and their endpoints */
+    }
     if (o->fan && validate_fan(o, world, err)) return 1;
     if (o->fan_lat_cap >= 0 && o->fan != 2) {
         fprintf(err, "invalid -P %d without -m 2: per-link latencies are recorded by the lock-step LL fan exchange only\n",

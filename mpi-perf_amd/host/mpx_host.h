@@ -55,6 +55,13 @@ typedef struct mpxh_options {
                                            link's per-iteration exchange latency
                                            (mpx_fan_lat_*), lat-*.csv; -1
                                            (default) = off                    */
+    int hostlink;                   /* -H  1|2: every rank is a GPU rank paired
+                                           with a host endpoint of its own, rank
+                                           world + r (mpx_xfer_hostlink /
+                                           mpx_host_xfer); 1 = the GPU rank is
+                                           group 1 (sends first), 2 = group 0 */
+    int procs;                      /* set by the host before mpxh_validate: 1 =
+                                           one process per rank (a launcher)  */
 } mpxh_options;
 
 /* parse status */
@@ -69,7 +76,7 @@ enum {
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:m:P:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:P:H:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -82,6 +89,8 @@ const char *mpxh_engine_name(int e);
 #define MPXH_FAN_ALIGN 4096
 /* -m 2: the largest -b (MPX_FAN_LL_MAX, include/mpx.h) */
 #define MPXH_FAN_LL_MAX 4096
+/* -H: a rank's host endpoint is rank world + r of the same context */
+#define MPXH_HOSTLINK_MAX_WORLD (MPXH_MAX_RANKS / 2)
 size_t mpxh_fan_stride(int buff_len);
 /* bytes of a fan run's tx (and rx): world blocks; 0 if that exceeds the
    largest length a rank can attach (2^31 - 1) or an argument is negative */
@@ -93,7 +102,10 @@ int mpxh_fan_peers(int world, int rank, int *peers);
 /* validate -L against -x / -e (the recorder traces the kernel engine's
    blocking loops only) and -m 1 against -a 1, an explicit -A 1, -L, -e, -d 1
    and a -b too large for world blocks (-m 2: the same, and a -b above
-   MPXH_FAN_LL_MAX), and -P without -m 2; then group_size, mpi_perf.c:399-403.
+   MPXH_FAN_LL_MAX), and -P without -m 2; -H against -x 1, -a 1, -m, an
+   explicit -A 1, -L, -d 1, -e sdma|rccl, processes mode and -w above
+   MPXH_HOSTLINK_MAX_WORLD; then group_size, mpi_perf.c:399-403 (with -H the
+   job is the 2 * world ranks: the GPU ranks and their endpoints).
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides
    by zero here (ppn == 0 in bidirectional mode): the caller raises SIGFPE. */

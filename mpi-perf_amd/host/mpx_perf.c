@@ -25,7 +25,11 @@
  * -a 1 every run is one round of the circle-method all-pairs schedule; with
  * -m 1 every run is one fan exchange: every rank with all the others at once
  * (mpx_xfer_fan, kernel engine), any world >= 2; -m 2 the same as a lock-step
- * exchange of LL granules (MPX_FAN_LL, -b up to 4096).
+ * exchange of LL granules (MPX_FAN_LL, -b up to 4096).  With -H 1|2 (threads
+ * mode, kernel engine) each of the -w ranks is a GPU rank paired with a CPU
+ * endpoint of its own across the host link (rank world + r, its loop on a
+ * thread of its own: mpx_xfer_hostlink / mpx_host_xfer); the job is then
+ * those 2 * w ranks, the GPU ranks group 1 (-H 1) or group 0 (-H 2).
  *
  * Built with -DMPX_WINDOWS_CLI (bin/mpx_perf_win), the front end is the
  * Windows / MS-MPI variant's (/root/reference/windows/mpi-perf.cpp):
@@ -129,6 +133,45 @@ static double wtime(void) /* MPI_Wtime */
 }
 
 static int is_root(void) { return !procs || me == 0; }
+
+/* -H: ranks [0, gpu_world) are GPU ranks, [gpu_world, world) their host
+   endpoints (0 without -H: every rank is a GPU rank) */
+static int gpu_world;
+static int is_endpoint(int r) { return opt.hostlink && r >= gpu_world; } /* (its tx_of[r] is a CPU pointer) */
+
+/* MPX_FILL_SPLITMIX / MPX_FILL_BYTE (include/mpx.h enum mpx_fill) on the CPU, for an endpoint's tx */
+static uint64_t mix64(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+static void host_fill(unsigned char *p, size_t n, int pattern, uint64_t arg)
+{
+    if (pattern == MPX_FILL_BYTE) {
+        memset(p, (int)(arg & 0xff), n);
+        return;
+    }
+    for (size_t k = 0; 8 * k < n; ++k) {
+        const uint64_t w = mix64((arg ^ k) + 0x9E3779B97F4A7C15ull);
+        for (size_t b = 0; b < 8 && 8 * k + b < n; ++b) p[8 * k + b] = (unsigned char)(w >> (8 * b));
+    }
+}
+/* mpx_fill / mpx_checksum of rank r's tx, wherever it lives */
+static void fill_tx(int r, size_t n, int pattern, uint64_t arg)
+{
+    if (is_endpoint(r))
+        host_fill((unsigned char *)tx_of[r], n, pattern, arg);
+    else
+        MPX_CHECK(mpx_fill(ctx, dev_of[r], tx_of[r], n, pattern, arg));
+}
+static void checksum_tx(int r, size_t n, uint64_t *out)
+{
+    if (is_endpoint(r))
+        MPX_CHECK(mpx_host_checksum(tx_of[r], n, out));
+    else
+        MPX_CHECK(mpx_checksum(ctx, dev_of[r], tx_of[r], n, out));
+}
 
 static void boot_failed(void)
 {
@@ -346,12 +389,11 @@ static void *rank_main(void *arg)
             if (!opt.use_dotnet) {
                 /* tx content per group (mpi_perf.c:244-251) or a seeded pattern */
                 if (opt.check == 2) {
-                    MPX_CHECK(mpx_fill(ctx, dev_of[r], tx_of[r], (size_t)B, MPX_FILL_SPLITMIX,
-                                       mpx_pattern_key(MPX_PATTERN_SEED, (unsigned)r, (unsigned)peer,
-                                                       (unsigned)run_idx)));
+                    fill_tx(r, (size_t)B, MPX_FILL_SPLITMIX,
+                            mpx_pattern_key(MPX_PATTERN_SEED, (unsigned)r, (unsigned)peer, (unsigned)run_idx));
                     prev_group = -1;
                 } else if (group != prev_group) {
-                    MPX_CHECK(mpx_fill(ctx, dev_of[r], tx_of[r], (size_t)B, MPX_FILL_BYTE, group ? 'b' : 'a'));
+                    fill_tx(r, (size_t)B, MPX_FILL_BYTE, group ? 'b' : 'a');
                     prev_group = group;
                 }
             }
@@ -364,8 +406,8 @@ static void *rank_main(void *arg)
             if (opt.check && !opt.use_dotnet) {
                 /* expected payloads: the peer's tx, read after every fill */
                 uint64_t s, s1;
-                MPX_CHECK(mpx_checksum(ctx, dev_of[r], tx_of[r], (size_t)B, &s));
-                MPX_CHECK(mpx_checksum(ctx, dev_of[r], tx_of[r], 1, &s1));
+                checksum_tx(r, (size_t)B, &s);
+                checksum_tx(r, 1, &s1);
                 share_tx_checksums(r, s, s1);
                 xo.check = 1;
                 xo.expect_checksum = txsum_of[peer];
@@ -375,14 +417,15 @@ static void *rank_main(void *arg)
             /* SDMA engine: capture this (mode, peer, B)'s graph chunks now, not
                inside the timed call (the reference's timer brackets only the
                loop, mpi_perf.c:501-533) */
-            if (!opt.use_dotnet) MPX_CHECK(mpx_xfer_prepare(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo));
+            if (!opt.use_dotnet && !opt.hostlink)
+                MPX_CHECK(mpx_xfer_prepare(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo));
             /* -L: every run's distribution is its own (before the arm: an
                armed rank's recorder cannot be touched) */
             if (lat) MPX_CHECK(mpx_lat_reset(ctx, r));
             /* -A 1: the run's kernel is launched now and started by the
                mpx_xfer_ex after the barrier (MPI_Start of a persistent
                request), so the launch is not inside the timed loop */
-            if (!opt.use_dotnet && opt.arm)
+            if (!opt.use_dotnet && opt.arm && !opt.hostlink) /* (a host-link call cannot be armed) */
                 MPX_CHECK(mpx_xfer_arm(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo));
             start_barrier(); /* MPI_Barrier, mpi_perf.c:499 */
             const double t_start = wtime();
@@ -392,6 +435,10 @@ static void *rank_main(void *arg)
                 char line[512];
                 mpxh_format_dotnet(line, sizeof line, group, r, peer, ip_of[peer], ip_of[r], B, opt.iters, opt.ppn);
                 fputs(line, stderr);
+            } else if (is_endpoint(r)) { /* -H: the endpoint's side, on this thread */
+                MPX_CHECK(mpx_host_xfer(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo, &tm));
+            } else if (opt.hostlink) {
+                MPX_CHECK(mpx_xfer_hostlink(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
             } else {
                 MPX_CHECK(mpx_xfer_ex(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
             }
@@ -416,10 +463,14 @@ static void *rank_main(void *arg)
                     fprintf(files.gpu_fp, "%s,%s,%d,%s,%d,%d,%d,%d,%d,%d,%.4f,%.4f,%.3f,%s,%d,%llu,%d,%lld,%llu,%llu,%s,%s\n", ts,
                             opt.uuid, r, mpxh_engine_name(opt.engine), xfer_mode(), dev_of[r], peer, dev_of[peer], B,
                             opt.iters, my_time * 1e3, tm.device_s * 1e3, gbps,
-                            (tm.protocol >= 0 && tm.protocol <= 9) ? proto[tm.protocol] : "?", tm.nwg,
+                            (tm.protocol >= 0 && tm.protocol <= 9) ? proto[tm.protocol]
+                            : tm.protocol == 11                    ? "host_ll"
+                            : tm.protocol == 12                    ? "host_bulk"
+                                                                   : "?",
+                            tm.nwg,
                             (unsigned long long)tm.check_iters, tm.check_failures, run_idx,
                             (unsigned long long)tm.recv_done, (unsigned long long)tm.recv_digest,
-                            (opt.arm && opt.engine == MPX_ENGINE_KERNEL) ? "armed" : "inline", rccl_build);
+                            (opt.arm && opt.engine == MPX_ENGINE_KERNEL && !opt.hostlink) ? "armed" : "inline", rccl_build);
                 }
                 if (lat && files.lat_fp) {
                     mpx_lat l;
@@ -674,7 +725,7 @@ int main(int argc, char **argv)
     }
     if (pst == MPXH_PARSE_BAD_VALUE) {
         if (is_root()) {
-            fprintf(stderr, "bad value for -e / -S / -L / -P\n");
+            fprintf(stderr, "bad value for -e / -S / -L / -P / -H\n");
             mpxh_print_usage(stderr);
         }
         mpx_abort();
@@ -707,9 +758,14 @@ int main(int argc, char **argv)
     }
     /* rank 0 validates (mpi_perf.c:399-403); the others see the same values */
     FILE *quiet = is_root() ? stderr : fopen("/dev/null", "w");
+    opt.procs = procs;
     const int v = mpxh_validate(&opt, world, quiet ? quiet : stderr);
     if (v == 2) raise(SIGFPE);
     if (v) mpx_abort();
+    if (opt.hostlink) { /* the job: the GPU ranks, then their endpoints (validated: threads mode, world <= 32) */
+        gpu_world = world;
+        world *= 2;
+    }
     char *group1 = NULL;
     if (is_root()) {
         group1 = win_cli ? mpxh_read_group1_windows(opt.group1_hostfile, opt.group_size)
@@ -789,6 +845,15 @@ int main(int argc, char **argv)
     else
         mpxh_pairing(world, group_of, grank_of, gsize_of, peer_of);
     free(group1);
+    if (opt.hostlink) { /* -H fixes the groups: GPU rank r with endpoint world + r */
+        for (int r = 0; r < world; ++r) {
+            const int gpu_side = r < gpu_world;
+            group_of[r] = (opt.hostlink == 1) == gpu_side ? 1 : 0;
+            peer_of[r] = gpu_side ? r + gpu_world : r - gpu_world;
+            grank_of[r] = r % gpu_world;
+            gsize_of[r] = gpu_world;
+        }
+    }
 
     if (win_cli && !opt.all_pairs && !opt.fan) {
         /* every rank prints its INFO line to stdout right after the pairing
@@ -820,15 +885,18 @@ int main(int argc, char **argv)
     if (procs) check_pairs_share_a_node();
     if (!procs) { /* threads mode: rank r on GPU -g[r], else r mod #GPUs */
         if (!opt.use_dotnet) MPX_CHECK(mpx_device_count(&ndev));
+        const int ngpu = opt.hostlink ? gpu_world : world; /* (-H: -g lists the GPU ranks' GPUs) */
         if (opt.gpus[0]) {
-            if (ngl < world) {
-                fprintf(stderr, "-g lists fewer GPUs than ranks (%d)\n", world);
+            if (ngl < ngpu) {
+                fprintf(stderr, "-g lists fewer GPUs than ranks (%d)\n", ngpu);
                 mpx_abort();
             }
-            for (int r = 0; r < world; ++r) dev_of[r] = gl[r];
+            for (int r = 0; r < ngpu; ++r) dev_of[r] = gl[r];
         } else {
-            for (int r = 0; r < world; ++r) dev_of[r] = r % ndev;
+            for (int r = 0; r < ngpu; ++r) dev_of[r] = r % ndev;
         }
+        for (int r = 0; r < world; ++r)
+            if (is_endpoint(r)) dev_of[r] = dev_of[peer_of[r]]; /* (the GPU at the other end of its link) */
         for (int r = 0; r < world; ++r) {
             if (dev_of[r] >= ndev) {
                 fprintf(stderr, "rank %d: GPU %d not visible (%d GPUs)\n", r, dev_of[r], ndev);
@@ -885,6 +953,11 @@ int main(int argc, char **argv)
         MPX_CHECK(mpx_init(world, opt.engine, &ctx));
         for (int r = 0; r < world; ++r) {
             if (procs && r != me) continue;
+            if (is_endpoint(r)) { /* -H: pinned host memory, zeroed */
+                MPX_CHECK(mpx_host_attach(ctx, r, (size_t)maxb));
+                MPX_CHECK(mpx_host_buffers(ctx, r, &tx_of[r], NULL)); /* (rx is the library's to fill) */
+                continue;
+            }
             MPX_CHECK(mpx_alloc(ctx, dev_of[r], (size_t)maxb, &tx_of[r]));
             MPX_CHECK(mpx_alloc(ctx, dev_of[r], (size_t)maxb, &rx_of[r]));
             MPX_CHECK(mpx_fill(ctx, dev_of[r], rx_of[r], (size_t)maxb, MPX_FILL_BYTE, 0));
@@ -928,6 +1001,7 @@ int main(int argc, char **argv)
 
     if (!opt.use_dotnet) {
         for (int r = 0; r < world; ++r) {
+            if (is_endpoint(r)) continue; /* (mpx_finalize frees an endpoint's memory) */
             MPX_CHECK(mpx_free(ctx, tx_of[r]));
             MPX_CHECK(mpx_free(ctx, rx_of[r]));
         }

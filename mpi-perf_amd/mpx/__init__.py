@@ -34,6 +34,9 @@ XFER_NOSTAGE = 4
 XFER_FAN_LL = 8      # MPX_FAN_LL (mpx_fan_opts.flags): the lock-step LL fan exchange
 FAN_LL_MAX = 4096    # MPX_FAN_LL_MAX: its largest block_len
 PROTO_FAN_LL = 10    # mpx_timing.protocol of such a call
+PROTO_HOSTLINK_LL = 11     # a host-link call (xfer_hostlink / host_xfer) with LL granules
+PROTO_HOSTLINK_BULK = 12   # a host-link call above the LL threshold
+HOSTLINK_HEADER_PATH = os.path.join(PKG_ROOT, "csrc", "mpx_hostlink.h")
 ABI_VERSION = 7
 PATTERN_SEED = 0x6D70695F70657266
 MAX_RANKS = 64
@@ -72,6 +75,23 @@ class XferOpts(C.Structure):
         ("timeout_ms", C.c_uint32),
         ("nwg", C.c_int32),
     ]
+
+
+class HostBox(C.Structure):
+    """hostlink::HostBox (csrc/mpx_hostlink.h): one direction of a host
+    endpoint's mailbox, rows indexed by the GPU peer's rank"""
+    _fields_ = [
+        ("flag", C.c_uint64 * 256 * 64),
+        ("ll", C.c_uint64 * 2048 * 64),
+        ("credit", C.c_uint64 * 256 * 64),
+        ("posted", C.c_uint64 * 64),
+        ("ready", C.c_uint64 * 64),
+    ]
+
+
+class HostMailbox(C.Structure):
+    """hostlink::HostMailbox: `in` is written by the GPU, `out` by the CPU"""
+    _fields_ = [("in", HostBox), ("out", HostBox)]
 
 
 class FanOpts(C.Structure):
@@ -214,6 +234,14 @@ _SIGS = {
     "mpx_fan_lat_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "mpx_fan_lat_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Lat)]),
     "mpx_fan_lat_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
+    "mpx_host_attach": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t]),
+    "mpx_host_buffers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "mpx_xfer_hostlink": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.POINTER(XferOpts), C.POINTER(Timing)]),
+    "mpx_host_xfer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(XferOpts),
+                                C.POINTER(Timing)]),
+    "mpx_host_checksum": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "mpx_hostlink_ll_max": (C.c_int, []),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mpx_rccl_get_unique_id": (C.c_int, [C.c_void_p]),
     "mpx_rccl_init_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -274,6 +302,29 @@ def fan_width(nranks: int, block_len: int, same_device: bool = True, nwg: int = 
     return lib().mpx_fan_width(nranks, block_len, 1 if same_device else 0, nwg)
 
 
+def host_checksum(data, offset: int = 0, n: int | None = None) -> int:
+    """mpx_host_checksum: mpx_checksum's value of n bytes of `data` (bytes, or
+    any writable buffer such as host_buffers' arrays) from `offset`, on the CPU"""
+    if isinstance(data, (bytes, bytearray)):
+        buf = (C.c_ubyte * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+        size = len(data)
+    else:
+        buf = (C.c_ubyte * max(len(data), 1)).from_buffer(data)
+        size = len(data)
+    if n is None:
+        n = size - offset
+    if offset < 0 or n < 0 or offset + n > size:
+        raise ValueError("host_checksum: range outside the data")
+    out = C.c_uint64()
+    check(lib().mpx_host_checksum(C.c_void_p(C.addressof(buf) + offset), n, C.byref(out)), "mpx_host_checksum")
+    return out.value
+
+
+def hostlink_ll_max() -> int:
+    """mpx_hostlink_ll_max: the host link's LL threshold in force (MPX_HOSTLINK_LL)"""
+    return lib().mpx_hostlink_ll_max()
+
+
 def shutdown() -> None:
     """mpx_shutdown: destroy the pooled rank streams (no context alive)."""
     check(lib().mpx_shutdown(), "mpx_shutdown")
@@ -313,6 +364,7 @@ class Context:
         self.engine = engine
         self._lat_cap = {}   # rank -> raw_cap of its latency recorder (lat_enable)
         self._fan_lat_cap = {}   # rank -> raw_cap of its link recorder (fan_lat_enable)
+        self._host_len = {}      # host endpoint -> its attached length (host_attach)
 
     def close(self) -> None:
         if self.h:
@@ -412,6 +464,53 @@ class Context:
             e.timing, e.links = t, out
             raise e
         return t, out
+
+    # host link (include/mpx_hostlink.h)
+    def host_attach(self, rank: int, length: int) -> None:
+        """mpx_host_attach: make `rank` a host endpoint with pinned tx / rx of `length` bytes"""
+        check(self.L.mpx_host_attach(self.h, rank, length), "mpx_host_attach")
+        self._host_len[rank] = length
+
+    def host_buffers(self, rank: int):
+        """mpx_host_buffers: the endpoint's (tx, rx) as writable ctypes byte
+        arrays over its pinned memory (valid until close)"""
+        tx, rx = C.c_void_p(), C.c_void_p()
+        check(self.L.mpx_host_buffers(self.h, rank, C.byref(tx), C.byref(rx)), "mpx_host_buffers")
+        n = max(self._host_len[rank], 16)
+        return (C.c_ubyte * n).from_address(tx.value), (C.c_ubyte * n).from_address(rx.value)
+
+    def _hostlink_opts(self, check_payload, expect, expect_ack, timeout_ms, nwg, stage) -> XferOpts:
+        return XferOpts(check=1 if check_payload else 0, flags=0 if stage else XFER_NOSTAGE, expect_checksum=expect,
+                        expect_ack=expect_ack, timeout_ms=timeout_ms, nwg=nwg)
+
+    def xfer_hostlink(self, mode: int, group: int, my_rank: int, host_rank: int, iters: int, tx: Buffer, rx: Buffer,
+                      length: int, check_payload: bool = False, expect: int = 0, expect_ack: int = 0,
+                      timeout_ms: int = 0, nwg: int = 0, stage: bool = True) -> Timing:
+        """mpx_xfer_hostlink: GPU rank my_rank's side of the loop with host
+        endpoint host_rank.  A failing call raises MpxError carrying .timing"""
+        o = self._hostlink_opts(check_payload, expect, expect_ack, timeout_ms, nwg, stage)
+        t = Timing()
+        st = self.L.mpx_xfer_hostlink(self.h, mode, group, my_rank, host_rank, iters, C.c_void_p(tx.ptr),
+                                      C.c_void_p(rx.ptr), length, C.byref(o), C.byref(t))
+        if st != OK:
+            e = MpxError(st, "mpx_xfer_hostlink")
+            e.timing = t
+            raise e
+        return t
+
+    def host_xfer(self, mode: int, group: int, host_rank: int, peer_rank: int, iters: int, length: int,
+                  check_payload: bool = False, expect: int = 0, expect_ack: int = 0, timeout_ms: int = 0,
+                  nwg: int = 0) -> Timing:
+        """mpx_host_xfer: host endpoint host_rank's side of the same loop, on
+        the calling thread (ctypes releases the GIL for the call)"""
+        o = self._hostlink_opts(check_payload, expect, expect_ack, timeout_ms, nwg, True)
+        t = Timing()
+        st = self.L.mpx_host_xfer(self.h, mode, group, host_rank, peer_rank, iters, length, C.byref(o), C.byref(t))
+        if st != OK:
+            e = MpxError(st, "mpx_host_xfer")
+            e.timing = t
+            raise e
+        return t
 
     def arm(self, mode: int, group: int, my_rank: int, peer_rank: int, iters: int, tx: Buffer, rx: Buffer,
             length: int, check_payload: bool = False, expect: int = 0, expect_ack: int = 0, timeout_ms: int = 0,

@@ -1,0 +1,200 @@
+"""The host link measured: a GPU rank and a CPU endpoint across PCIe, on ONE GPU.
+
+Rank 0 is a GPU rank on GPU 0, rank 1 a host endpoint (include/mpx_hostlink.h);
+each side of a call runs on a thread of its own behind a barrier.  Unlike the
+loopback figures of the other probes there IS a link in these: every payload
+crosses PCIe between HBM and pinned host memory.  One JSON line per item:
+
+    latency    8 B ping-pong half round trip, both orientations: 5 calls of
+               2000 iterations after a warm-up call; median, min and max.
+               The time is the GPU kernel's own clock (mpx_last_phases:
+               kernel_s - posted_wait_s, so neither the launch nor the wait
+               for the endpoint's thread is in it) over 2 * iters.
+    bandwidth  unidir at 4 MiB in each direction, widths 1 ... 128 and the
+               default width: 3 calls of 50 iterations after a warm-up, best
+               and median, GB/s = bytes / the same kernel time, and as a
+               fraction of PCIe Gen5 x16's 63 GB/s.  Beside it hipMemcpyAsync
+               between the same pinned and device buffers (the runtime's copy
+               engine), 50 copies and one synchronise under a host clock, in
+               the same process.
+    threshold  ping-pong half round trip at 256 B ... 8 KiB, forced LL
+               (MPX_HOSTLINK_LL=8192) against forced bulk (MPX_HOSTLINK_LL=0),
+               median of 5 calls of 1000 iterations; the largest size at which
+               LL is not slower than bulk.
+    numa       the node of the endpoint's pinned memory and of the threads'
+               CPUs, and the GPU's.  Nothing is bound: the line says so.
+
+No pass mark; nothing here is asserted anywhere.
+
+    python tools/hostlink_probe.py > profiles/hostlink.jsonl
+"""
+import argparse
+import ctypes as C
+import glob
+import json
+import os
+import statistics
+import sys
+import threading
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--calls", type=int, default=5)
+ap.add_argument("--bw-bytes", type=int, default=4 << 20)
+ap.add_argument("--bw-iters", type=int, default=50)
+args = ap.parse_args()
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-perf_amd"))
+import mpx  # noqa: E402
+
+CAP = max(args.bw_bytes, 8192) + 4096
+PCIE_SPEC_GBPS = 63.0
+G, E = 0, 1
+KIND = "host link (GPU 0 <-> pinned host memory over PCIe); no pass mark"
+os.environ.pop("MPX_HOSTLINK_LL", None)
+os.environ.pop("MPX_HOSTLINK_WG", None)
+
+hip = C.CDLL("libamdhip64.so.7")
+hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+hip.hipDeviceSynchronize.argtypes = []
+libc = C.CDLL(None, use_errno=True)
+
+c = mpx.Context(2, "kernel")
+gtx, grx = c.alloc(0, CAP), c.alloc(0, CAP)
+c.fill(gtx, CAP, mpx.FILL_SPLITMIX, 11)
+c.attach(G, 0, gtx, grx, CAP)
+c.host_attach(E, CAP)
+htx, hrx = c.host_buffers(E)
+for k in range(0, CAP, 4096):
+    htx[k] = k & 0xff
+cpu_of = {}
+
+
+def call(mode, gpu_group, n, iters, nwg=0):
+    """one call, both sides; (the GPU side's loop seconds on the kernel's clock, its Timing, the endpoint's)"""
+    out, errs = {}, []
+    bar = threading.Barrier(2)
+
+    def side(r):
+        try:
+            cpu_of[r] = libc.sched_getcpu()
+            bar.wait()
+            if r == G:
+                out[r] = c.xfer_hostlink(mode, gpu_group, G, E, iters, gtx, grx, n, timeout_ms=20000, nwg=nwg)
+            else:
+                out[r] = c.host_xfer(mode, 1 - gpu_group, E, G, iters, n, timeout_ms=20000, nwg=nwg)
+        except Exception as e:  # noqa: BLE001
+            errs.append(f"rank {r}: {e}")
+            bar.abort()
+    th = [threading.Thread(target=side, args=(r,)) for r in (G, E)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    if errs:
+        raise RuntimeError("; ".join(errs))
+    ph = c.phases(G)
+    return ph["kernel_s"] - ph["posted_wait_s"], out[G], out[E]
+
+
+def spread(v, scale, digits=3):
+    return dict(median=round(statistics.median(v) * scale, digits), min=round(min(v) * scale, digits),
+                max=round(max(v) * scale, digits))
+
+
+# ---- latency ------------------------------------------------------------------
+for gpu_group in (1, 0):
+    call(mpx.MODE_PINGPONG, gpu_group, 8, 2000)
+    v = [call(mpx.MODE_PINGPONG, gpu_group, 8, 2000)[0] / 2000 / 2 for _ in range(args.calls)]
+    print(json.dumps(dict(kind=KIND, item="latency", bytes=8, mode="pingpong", gpu_group=gpu_group, calls=args.calls,
+                          iters=2000, half_rtt_us=spread(v, 1e6), clock="kernel (s_memrealtime), posted wait excluded",
+                          ll_threshold=mpx.hostlink_ll_max())), flush=True)
+
+# ---- bandwidth ----------------------------------------------------------------
+B, IT = args.bw_bytes, args.bw_iters
+best_width = {}
+for gpu_group, direction in ((1, "device_to_host"), (0, "host_to_device")):
+    rows = []
+    for nwg in (0, 1, 2, 4, 8, 16, 32, 64, 128):
+        call(mpx.MODE_UNIDIR, gpu_group, B, 5, nwg)
+        res = [call(mpx.MODE_UNIDIR, gpu_group, B, IT, nwg) for _ in range(3)]
+        gbps = [B * IT / r[0] / 1e9 for r in res]
+        rows.append(dict(nwg_asked=nwg, nwg=res[0][1].nwg, GBps_best=round(max(gbps), 2),
+                         GBps_median=round(statistics.median(gbps), 2),
+                         fraction_of_63GBps_spec=round(max(gbps) / PCIE_SPEC_GBPS, 3)))
+    swept = [r for r in rows if r["nwg_asked"]]
+    best = max(swept, key=lambda r: r["GBps_median"])
+    best_width[direction] = best["nwg"]
+    print(json.dumps(dict(kind=KIND, item="bandwidth", mode="unidir", direction=direction, bytes=B, iters=IT, calls=3,
+                          default_width=rows[0], sweep=swept, best_width=best["nwg"],
+                          clock="kernel (s_memrealtime), posted wait excluded")), flush=True)
+
+# the runtime's copy engine between the same buffers
+import time  # noqa: E402
+
+for direction, dst, src, kind in (("device_to_host", C.addressof(hrx), grx.ptr, 2),
+                                  ("host_to_device", grx.ptr, C.addressof(htx), 1)):
+    v = []
+    for rep in range(4):
+        hip.hipDeviceSynchronize()
+        t0 = time.perf_counter()
+        for _ in range(IT):
+            rc = hip.hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), B, kind, None)
+            assert rc == 0, rc
+        assert hip.hipDeviceSynchronize() == 0
+        if rep:
+            v.append(B * IT / (time.perf_counter() - t0) / 1e9)
+    print(json.dumps(dict(kind=KIND, item="bandwidth_reference", what="hipMemcpyAsync, the same pinned and device buffers",
+                          direction=direction, bytes=B, copies=IT, calls=3, GBps_best=round(max(v), 2),
+                          GBps_median=round(statistics.median(v), 2),
+                          fraction_of_63GBps_spec=round(max(v) / PCIE_SPEC_GBPS, 3),
+                          clock="host clock around the copies and one synchronise")), flush=True)
+
+# ---- the LL threshold ---------------------------------------------------------
+sizes = [256 << k for k in range(6)]
+for gpu_group in (1, 0):
+    rows, chosen = [], None
+    for n in sizes:
+        row = dict(bytes=n)
+        for name, value in (("ll", "8192"), ("bulk", "0")):
+            os.environ["MPX_HOSTLINK_LL"] = value
+            call(mpx.MODE_PINGPONG, gpu_group, n, 200)
+            v = [call(mpx.MODE_PINGPONG, gpu_group, n, 1000)[0] / 1000 / 2 for _ in range(args.calls)]
+            row[name + "_half_rtt_us"] = spread(v, 1e6)
+        os.environ.pop("MPX_HOSTLINK_LL", None)
+        if row["ll_half_rtt_us"]["median"] <= row["bulk_half_rtt_us"]["median"]:
+            chosen = n
+        rows.append(row)
+    print(json.dumps(dict(kind=KIND, item="ll_threshold", mode="pingpong", gpu_group=gpu_group, calls=args.calls, iters=1000,
+                          sweep=rows, largest_size_where_ll_is_not_slower=chosen, in_force=mpx.hostlink_ll_max())),
+          flush=True)
+
+# ---- NUMA ---------------------------------------------------------------------
+
+
+def node_of_cpu(cpu):
+    for d in glob.glob("/sys/devices/system/node/node[0-9]*"):
+        for part in open(os.path.join(d, "cpulist")).read().strip().split(","):
+            lo, _, hi = part.partition("-")
+            if part and int(lo) <= cpu <= int(hi or lo):
+                return int(d.rsplit("node", 1)[1])
+    return None
+
+
+def node_of_page(addr):
+    """move_pages(2) with no target nodes: the node each page is on"""
+    page = C.c_void_p(addr & ~4095)
+    status = C.c_int(-1)
+    rc = libc.syscall(279, 0, C.c_ulong(1), C.byref(page), None, C.byref(status), 0)
+    return status.value if rc == 0 else None
+
+
+try:
+    gpu_node = int(open(f"/sys/bus/pci/devices/{mpx.bus_id(0).lower()}/numa_node").read())
+except OSError:
+    gpu_node = None
+print(json.dumps(dict(kind=KIND, item="numa", binding="not controlled: no thread or allocation was bound to a node",
+                      gpu_numa_node=gpu_node, endpoint_tx_node=node_of_page(C.addressof(htx)),
+                      endpoint_rx_node=node_of_page(C.addressof(hrx)),
+                      gpu_side_thread=dict(cpu=cpu_of.get(G), node=node_of_cpu(cpu_of.get(G, -1))),
+                      endpoint_thread=dict(cpu=cpu_of.get(E), node=node_of_cpu(cpu_of.get(E, -1))),
+                      best_width=best_width)), flush=True)
+c.close()
