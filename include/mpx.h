@@ -228,7 +228,10 @@ int mpx_link_counters(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t out[4])
    environment (the once-per-process gate of the fault-injection knobs:
    mpx_perf and bench.py can never reach it); MPX_ERR_INVALID for a rank that
    is not local; MPX_ERR_STATE for a rank that holds an armed call or whose
-   transfer timed out. */
+   transfer timed out.
+   A host endpoint (mpx_hostlink.h) is accepted as my_rank too: its tx_seq,
+   rx_seq and calls towards peer_rank move; it has no token, so token_by must
+   be 0 (MPX_ERR_INVALID); MPX_ERR_STATE for an endpoint that timed out. */
 int mpx_test_advance_link(mpx_ctx *ctx, int my_rank, int peer_rank, uint64_t seq_by, uint64_t calls_by,
                           uint64_t token_by);
 

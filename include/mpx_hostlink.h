@@ -58,7 +58,9 @@
    mpx_last_phases works for it.  The CPU side reports wall_s from
    CLOCK_MONOTONIC, device_s = 0, launches = 0 and the link's nwg.
      mpx_link_counters accepts either end as my_rank (out[3] = 0 for a host
-   endpoint); the counters move as for a pair call.  Host-link calls are
+   endpoint); the counters move as for a pair call.  The test-only
+   mpx_test_advance_link accepts either end too (a host endpoint with
+   token_by = 0 only; both ends of a link must be advanced alike).  Host-link calls are
    never traced by the latency recorder (mpx_lat_*), like non-blocking calls,
    and cannot be armed.  MPX_TEST=skip_push=k loses the k-th B-byte payload of
    a sending side (never an LL ack).

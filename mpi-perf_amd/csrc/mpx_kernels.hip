@@ -1692,9 +1692,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
         ++txs;
         const bool lose = sends_n && a.skip_push == i + 1;   // test knob: a B-byte payload, never an ack
         if (ll_send) {
-            // a side that received a bulk payload answers once every chunk is in
-            if (!ll_recv && wg0 && !L.template poll_ge<false>(&a.gbar[kScrLanded], (u64)a.nwg * (u64)(i + 1), i))
-                return false;
+            // a side that received a bulk payload answers once every chunk is in:
+            // the chunks of the receives it has completed — i + 1 of them where it
+            // receives first, i where it sends first (none before its first send:
+            // the 0-byte unidir payload with a bulk ack, MPX_HOSTLINK_LL=0)
+            const u64 landed = (u64)a.nwg * (u64)(GROUP == 1 ? i : i + 1);
+            if (!ll_recv && wg0 && landed && !L.template poll_ge<false>(&a.gbar[kScrLanded], landed, i)) return false;
             if (!lose) L.push_ll(send_len, txs);
             else L.push_ll_tags_only(send_len, txs);
         } else {

@@ -1200,10 +1200,12 @@ int mpx_test_advance_link(mpx_ctx* ctx, int my_rank, int peer_rank, uint64_t seq
                           uint64_t token_by) {
     if (!ctx) return fail(MPX_ERR_INVALID, "NULL argument");
     if (!test_gate()) return fail(MPX_ERR_UNSUPPORTED, "mpx_test_advance_link: the process started without MPX_TEST");
-    if (my_rank < 0 || my_rank >= ctx->nranks || !ctx->r[my_rank].local)
+    // (either end of a host link, as mpx_link_counters: a host endpoint has no token to move)
+    if (my_rank < 0 || my_rank >= ctx->nranks || !(ctx->r[my_rank].local || ctx->r[my_rank].host))
         return fail(MPX_ERR_INVALID, "rank %d is not a local rank", my_rank);
     if (peer_rank < 0 || peer_rank >= ctx->nranks) return fail(MPX_ERR_INVALID, "peer rank %d", peer_rank);
     Rank& me = ctx->r[my_rank];
+    if (me.host && token_by) return fail(MPX_ERR_INVALID, "host endpoint %d has no token (token_by must be 0)", my_rank);
     if (me.armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", my_rank);
     if (me.broken) return fail(MPX_ERR_STATE, "rank %d: a previous transfer timed out", my_rank);
     const u64 top = ~0ull;

@@ -288,6 +288,29 @@ def test_refusals_on_a_live_context():
             assert status(c2.host_attach, 1, 64) == mpx.ERR_UNSUPPORTED
             assert L.mpx_host_xfer(c2.h, PP, 0, 1, 0, 1, 8, None, C.byref(t)) == mpx.ERR_UNSUPPORTED
             assert L.mpx_xfer_hostlink(c2.h, PP, 1, 0, 1, 1, None, None, 8, None, C.byref(t)) == mpx.ERR_UNSUPPORTED
+    # mpx_test_advance_link takes a host endpoint as my_rank (as mpx_link_counters does), with token_by = 0 only
+    was = [c.link_counters(0, 1), c.link_counters(1, 0)]
+    assert status(c.test_advance_link, 1, 0, 0, 0, 1) == mpx.ERR_INVALID                   # an endpoint has no token
+    assert status(c.test_advance_link, 1, 0, 1, 1, 1) == mpx.ERR_INVALID
+    assert status(c.test_advance_link, 1, 2, 1, 0, 0) == mpx.ERR_INVALID                   # peer out of range
+    assert status(c.test_advance_link, 1, 0, MASK, 0, 0) == mpx.ERR_INVALID                # past 2^64 (tx_seq > 0 by now)
+    assert [c.link_counters(0, 1), c.link_counters(1, 0)] == was and was[1]["tx_seq"] > 0
+    for a, b in ((0, 1), (1, 0)):                                                          # both ends alike: the link goes on
+        c.test_advance_link(a, b, 7, 2, 0)
+    now = [c.link_counters(0, 1), c.link_counters(1, 0)]
+    for k in (0, 1):
+        assert now[k] == dict(tx_seq=was[k]["tx_seq"] + 7, rx_seq=was[k]["rx_seq"] + 7, calls=was[k]["calls"] + 2,
+                              token=was[k]["token"]), (k, was[k], now[k])
+    out = run_ok(h, n, PP, 0, n, 3, check=True)
+    assert_call(h, out, PP, 0, n, 3, True)
+    # an endpoint that timed out is refused (MPX_ERR_STATE), as a GPU rank is
+    hb = HostLinks(64)
+    try:
+        assert status(hb.c.host_xfer, PP, 0, 1, 0, 1, 8, timeout_ms=50) == mpx.ERR_TIMEOUT
+        assert status(hb.c.test_advance_link, 1, 0, 1, 0, 0) == mpx.ERR_STATE
+        assert hb.c.link_counters(1, 0)["tx_seq"] == 0
+    finally:
+        hb.close()
 
 
 def test_phases_of_a_hostlink_call():

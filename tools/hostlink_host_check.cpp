@@ -6,8 +6,9 @@
 // the same protocol (what k_xfer_hostlink does with its pushes, polls, pulls
 // and credits) on malloc'ed memory.  Covered: both modes, both orientations,
 // sizes on both sides of the LL threshold, check mode, several calls on one
-// link, a lost payload in each direction and form, and a peer that never
-// comes (the CPU's deadline).
+// link, links that start just short of push 2^31, push 2^32 and call 2^32, a
+// lost payload in each direction and form, and a peer that never comes (the
+// CPU's deadline).
 #include "mpx_hostlink.h"
 
 #include <stdio.h>
@@ -253,6 +254,8 @@ int main() {
     EXPECT(ll_units(0) == 1 && ll_units(1) == 1 && ll_units(8) == 1 && ll_units(9) == 2 && ll_units(8192) == 1024);
     EXPECT(kDefaultLL <= kLLBytes && kDefaultMaxWG <= kWG && narrow_nwg(128, 4161) == 5 && narrow_nwg(7, 1 << 20) == 7 && narrow_nwg(4, 0) == 1);
     EXPECT(ll_tag(1) == 0x80000001u && ll_tag(0x80000000ull) == 0x80000000u);
+    EXPECT(ll_tag(0x7fffffffull) == 0xffffffffu && ll_tag(0xffffffffull) == 0xffffffffu);
+    EXPECT(ll_tag(1ull << 32) == 0x80000000u && ll_tag((1ull << 32) + 1) == 0x80000001u);
 
     // both modes, both orientations, sizes on both sides of the threshold, with and without check
     {
@@ -273,6 +276,36 @@ int main() {
         for (int mode : {0, 2})
             for (int cpu_group : {0, 1}) l.call(mode, cpu_group, 8192, 4, 1, 3);
     }
+    // The wrap points.  A link "near P": its next push is number P - 4.  Every
+    // case gets a fresh Link (a zeroed mailbox), so no LL message follows a
+    // larger one by a multiple of 2^31 pushes (the LL zone's documented alias).
+    // The boundary inside one call (9 iterations) and between two (4 + 4: the
+    // first call ends on push P - 1); with the call number starting at
+    // 2^32 - 2, so the second call of the 4 + 4 form posts 2^32.
+    for (uint64_t P : {1ull << 31, 1ull << 32})
+        for (int mode : {0, 2})
+            for (int cpu_group : {0, 1})
+                for (long long n : {8ll, 4161ll})
+                    for (uint64_t calls0 : {0ull, (1ull << 32) - 2}) {
+                        {
+                            Link l(8192);
+                            l.seq = P - 5;
+                            l.calls = calls0;
+                            l.call(mode, cpu_group, n, 9, 1, 4);
+                            EXPECT(l.seq == P + 4 && l.calls == calls0 + 1);
+                        }
+                        {
+                            Link l(8192);
+                            l.seq = P - 5;
+                            l.calls = calls0;
+                            l.call(mode, cpu_group, n, 4, 1, 4);
+                            EXPECT(l.seq == P - 1);
+                            l.call(mode, cpu_group, n, 0, 1, 4);   // (posts nothing, takes no number)
+                            l.call(mode, cpu_group, n, 4, 1, 4);
+                            l.call(mode, 1 - cpu_group, n, 2, 1, 4);
+                            EXPECT(l.seq == P + 5 && l.calls == calls0 + 3);
+                        }
+                    }
     // a lost payload: the receiver's checksum misses once, the sender's side is clean
     {
         Link l(8192);
