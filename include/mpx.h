@@ -114,7 +114,10 @@ typedef struct mpx_timing {
                                  pulled form, 9 = fan exchange (mpx_xfer_fan),
                                  10 = lock-step LL fan exchange (MPX_FAN_LL),
                                  11 = host link, LL granules, 12 = host link,
-                                 bulk (mpx_xfer_hostlink, mpx_host_xfer)        */
+                                 bulk (mpx_xfer_hostlink, mpx_host_xfer),
+                                 13 = host link, the full-duplex non-blocking
+                                 loop (mpx_xfer_hostlink_duplex,
+                                 mpx_host_xfer_duplex)                          */
     int32_t check_failures;   /* iterations whose payload checksum mismatched  */
     uint64_t check_iters;     /* iterations whose payload was checksummed      */
     /* receive accounting, as the reference's loop completes receives: every
@@ -502,6 +505,11 @@ int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
    mpx_host_checksum and mpx_hostlink_ll_max are declared, with their
    contract, in a header of their own, which is part of this one. */
 #include "mpx_hostlink.h"
+
+/* ---- host link: the non-blocking loop, full duplex across the link --------- */
+/* mpx_xfer_hostlink_duplex and mpx_host_xfer_duplex are declared, with their
+   contract, in a header of their own, which is part of this one. */
+#include "mpx_hostlink_duplex.h"
 
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of

@@ -36,7 +36,8 @@
    opts.timeout_ms against CLOCK_MONOTONIC (0 = 10 s).
      Statuses, all decided before any GPU work or wait:
        MPX_ERR_UNSUPPORTED  an SDMA or RCCL context; MPX_MODE_NONBLOCKING
-                            (the full-duplex loop is not built)
+                            (the full-duplex loop has entry points of its
+                            own: mpx_hostlink_duplex.h)
        MPX_ERR_INVALID      NULL arguments; a host_rank that is not a host
                             endpoint or a GPU rank that is not an attached
                             local rank; tx / rx other than the GPU rank's

@@ -2,7 +2,9 @@
 // endpoints (mpx_host_attach, mpx_host_buffers), the GPU side of a host-link
 // call (mpx_xfer_hostlink: the arguments of k_xfer_hostlink, launched through
 // the kernel engine's one call lifecycle, run_hostlink_kernel) and the CPU
-// side (mpx_host_xfer: mpx_hostlink.h's run() on the calling thread).
+// side (mpx_host_xfer: mpx_hostlink.h's run() on the calling thread); and the
+// full-duplex loop's two entry points (include/mpx_hostlink_duplex.h:
+// k_hostlink_duplex through run_hostlink_duplex_kernel, run_duplex()).
 #include "mpx_runtime.h"
 
 #include "mpx_hostlink.h"
@@ -260,6 +262,123 @@ int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_
         me.broken = true;
         return fail(MPX_ERR_TIMEOUT, "host endpoint %d <- rank %d: a CPU wait timed out at iteration %d (mode %d, %d B)",
                     host_rank, peer_rank, r.where, mode, buff_len);
+    }
+    me.tx_seq[peer_rank] += (u64)iters;
+    me.rx_seq[peer_rank] += (u64)iters;
+    if (r.check_failures)
+        return fail(MPX_ERR_CHECK, "host endpoint %d: %d of %llu received payloads failed the checksum", host_rank,
+                    r.check_failures, (unsigned long long)r.check_iters);
+    return MPX_OK;
+}
+
+// ---- the full-duplex loop (include/mpx_hostlink_duplex.h) ----------------------
+
+namespace {
+// check_hostlink's rules (there is no mode and no group), and a per-direction
+// width whose split grid fits
+int check_duplex(mpx_ctx* ctx, int gpu_rank, int host_rank, int iters, int buff_len, const mpx_xfer_opts* o) {
+    TRY(check_hostlink(ctx, MPX_MODE_PINGPONG, 0, gpu_rank, host_rank, iters, buff_len, o));
+    const int nwg = hostlink_nwg(o, buff_len);
+    if (nwg > kDuplexMaxWG)
+        return fail(MPX_ERR_INVALID, "nwg %d per direction: the split grid would exceed %d workgroups", nwg, kMaxPushWG);
+    return MPX_OK;
+}
+}  // namespace
+
+int mpx_xfer_hostlink_duplex(mpx_ctx* ctx, int my_rank, int host_rank, int iters, void* tx, void* rx, int buff_len,
+                             const mpx_xfer_opts* opts, mpx_timing* t) {
+    if (!ctx || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    const double t_call = now_s();
+    TRY(check_duplex(ctx, my_rank, host_rank, iters, buff_len, opts));
+    Rank& me = ctx->r[my_rank];
+    const Rank& host = ctx->r[host_rank];
+    if (!tx || !rx || tx != me.tx || rx != me.rx)
+        return fail(MPX_ERR_INVALID, "tx/rx are not rank %d's attached buffers", my_rank);
+    if (me.armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", my_rank);
+    if (me.broken) return fail(MPX_ERR_STATE, "rank %d: a previous transfer timed out", my_rank);
+    const bool check = opts && opts->check;
+    DeviceGuard g(me.dev);
+    HIPCK(g.err);
+    if (check) TRY(ensure_csum(me, iters));
+
+    const long long len = buff_len;
+    hostlink::HostMailbox* hm = static_cast<hostlink::HostMailbox*>(host.host_mb_dev);
+    XferArgs a{};
+    a.tx = me.tx;
+    a.rx = me.rx;
+    a.peer_rx = host.host_rx_dev;
+    a.peer_tx = host.host_tx_dev;
+    a.my_mb = reinterpret_cast<Mailbox*>(&hm->out);
+    a.peer_mb = reinterpret_cast<Mailbox*>(&hm->in);
+    a.status = me.status;
+    a.csum = me.csum;
+    a.gbar = me.scratch;
+    a.tx_seq0 = me.tx_seq[host_rank];
+    a.rx_seq0 = me.rx_seq[host_rank];
+    a.timeout_ticks = timeout_ticks(opts);
+    a.len = len;
+    a.iters = iters;
+    a.mode = MPX_MODE_NONBLOCKING;
+    a.my_slot = a.peer_slot = my_rank;
+    a.nwg = hostlink_nwg(opts, len);   // per direction
+    a.check = check ? 1 : 0;
+    a.nb_publish = nb_publish();
+    a.skip_push = test_knobs().skip_push;
+    if (!(opts && (opts->flags & MPX_XFER_NOSTAGE)) && len > 0) {
+        int per_block = 0;
+        if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, me.dev) != hipSuccess) per_block = 0;
+        const long long chunk = (((len + a.nwg - 1) / a.nwg) + 15) & ~15ll;
+        if (chunk <= kStageMaxBytes && chunk <= (long long)per_block - 1024) a.stage = (int)chunk;
+    }
+    TRY(run_hostlink_duplex_kernel(me, my_rank, host_rank, a, t_call, t));
+    t->bytes = 2ull * (uint64_t)buff_len * (uint64_t)iters;
+    if (!check || iters <= 0) return MPX_OK;
+    const uint64_t want = opts->expect_checksum;
+    return check_verdict(me, my_rank, 1, iters, (u64)len, &want, t, nullptr, nullptr);
+}
+
+int mpx_host_xfer_duplex(mpx_ctx* ctx, int host_rank, int peer_rank, int iters, int buff_len, const mpx_xfer_opts* opts,
+                         mpx_timing* t) {
+    if (!ctx || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    TRY(check_duplex(ctx, peer_rank, host_rank, iters, buff_len, opts));
+    Rank& me = ctx->r[host_rank];
+    if (me.broken) return fail(MPX_ERR_STATE, "host endpoint %d: a previous transfer timed out", host_rank);
+    const TestKnobs knobs = test_knobs();
+    hostlink::Call c;
+    c.mb = static_cast<hostlink::HostMailbox*>(me.host_mb);
+    c.tx = me.tx;
+    c.rx = me.rx;
+    c.gpu = peer_rank;
+    c.mode = MPX_MODE_NONBLOCKING;
+    c.iters = iters;
+    c.len = buff_len;
+    c.nwg = hostlink_nwg(opts, buff_len);
+    c.check = (opts && opts->check) ? 1 : 0;
+    c.expect = opts ? opts->expect_checksum : 0;
+    c.tx_seq0 = me.tx_seq[peer_rank];
+    c.rx_seq0 = me.rx_seq[peer_rank];
+    if (iters > 0) ++me.calls[peer_rank];   // (as mpx_host_xfer)
+    c.call = knobs.no_posted ? 0 : me.calls[peer_rank];
+    c.timeout_s = (opts && opts->timeout_ms ? opts->timeout_ms : 10000) * 1e-3;
+    hostlink::Result r;
+    const double t0 = now_s();
+    const int rc = hostlink::run_duplex(c, &r);
+    t->wall_s = now_s() - t0;
+    t->device_s = 0;
+    t->launches = 0;
+    t->nwg = c.nwg;
+    t->protocol = kProtoHostDuplex;
+    t->bytes = 2ull * (uint64_t)buff_len * (uint64_t)iters;
+    t->recv_done = r.recv_done;
+    t->recv_digest = r.recv_digest;
+    t->check_iters = r.check_iters;
+    t->check_failures = r.check_failures;
+    if (rc != 0) {
+        me.broken = true;
+        return fail(MPX_ERR_TIMEOUT, "host endpoint %d <- rank %d: a CPU wait timed out at iteration %d (full duplex, %d B)",
+                    host_rank, peer_rank, r.where, buff_len);
     }
     me.tx_seq[peer_rank] += (u64)iters;
     me.rx_seq[peer_rank] += (u64)iters;

@@ -399,22 +399,25 @@ int run_kernel(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank, i
     return complete_pair(me, kc, t_call, t);
 }
 
-// A host-link call (mpx_xfer_hostlink; its arguments are built in
-// mpx_engine_hostlink.hip): the same three steps with k_xfer_hostlink.
-int run_hostlink_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, int grid, bool ll, double t_call,
-                        mpx_timing* t) {
+// A host-link call (mpx_xfer_hostlink, mpx_xfer_hostlink_duplex; its arguments
+// are built in mpx_engine_hostlink.hip): the same three steps with the host
+// link's kernel, which `enqueue` launches.
+namespace {
+template <class Enqueue>
+int run_hostlink_call(Rank& me, int my_rank, int host_rank, XferArgs& a, int nwg, int protocol, double t_call,
+                      mpx_timing* t, Enqueue enqueue) {
     const TestKnobs knobs = test_knobs();
     Call c;
     c.my_rank = my_rank;
     c.iters = a.iters;
     c.kernel = "host-link kernel";
     c.fail_launch = knobs.fail_launch == my_rank;
-    c.nwg = ll ? 1 : a.nwg;
-    c.protocol = ll ? kProtoHostLL : kProtoHostBulk;
+    c.nwg = nwg;
+    c.protocol = protocol;
     if (a.check) c.csum_words = (size_t)a.iters;
     take_numbers(me, c, &host_rank, 1, knobs.no_posted, &a.call);
     a.done_token = c.token;
-    const int st = launch_call(me, c, [&] { return launch_hostlink(a, grid, me.stream); });
+    const int st = launch_call(me, c, enqueue);
     if (st != MPX_OK) {
         give_back(me, c);
         return st;
@@ -423,6 +426,19 @@ int run_hostlink_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, int g
         return fail(MPX_ERR_TIMEOUT, "rank %d <- host endpoint %d: device wait timed out at iteration %u (mode %d, %lld B)",
                     my_rank, host_rank, iteration, a.mode, a.len);
     });
+}
+}  // namespace
+
+int run_hostlink_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, int grid, bool ll, double t_call,
+                        mpx_timing* t) {
+    return run_hostlink_call(me, my_rank, host_rank, a, ll ? 1 : a.nwg, ll ? kProtoHostLL : kProtoHostBulk, t_call, t,
+                             [&] { return launch_hostlink(a, grid, me.stream); });
+}
+
+// the full-duplex loop (k_hostlink_duplex): a.nwg is the per-direction width
+int run_hostlink_duplex_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, double t_call, mpx_timing* t) {
+    return run_hostlink_call(me, my_rank, host_rank, a, a.nwg, kProtoHostDuplex, t_call, t,
+                             [&] { return launch_hostlink_duplex(a, me.stream); });
 }
 
 // Start the armed call: one host store; the kernel has been waiting for it.

@@ -1,9 +1,10 @@
 // mpx_hostlink.h — the host link's shared memory layout and the CPU endpoint's
-// side of the transfer loops (include/mpx_hostlink.h: mpx_host_xfer).  Plain
+// side of the transfer loops (include/mpx_hostlink.h: mpx_host_xfer;
+// include/mpx_hostlink_duplex.h: mpx_host_xfer_duplex).  Plain
 // C++: no HIP include, every shared word is a uint64_t read and written
 // through the __atomic_* builtins, so the file builds with g++ alone
-// (tools/hostlink_host_check.cpp runs it under the host sanitizers with a
-// second CPU thread in the GPU's place).
+// (tools/hostlink_host_check.cpp and tools/hostlink_duplex_host_check.cpp run
+// it under the host sanitizers with a second CPU thread in the GPU's place).
 //
 // A host endpoint cannot write device memory, so every word and byte that
 // crosses the link lives in pinned host memory and the GPU does all the
@@ -55,7 +56,9 @@ struct HostBox {
     uint64_t ready[kRanks];           // "tx holds message k"
 };
 // in : written by the GPU, read by the CPU   — flag, ll, credit, posted
-// out: written by the CPU, polled by the GPU — ll (the ll_out row), ready, posted
+// out: written by the CPU, polled by the GPU — ll (the ll_out row), ready, posted,
+//      and credit[gpu][0] (the full-duplex loop's check mode: the last of the
+//      GPU's pushes the CPU has checked and poisoned)
 struct HostMailbox {
     HostBox in;
     HostBox out;
@@ -262,6 +265,101 @@ inline int run(const Call& c, Result* r) {
             return 1;
         }
     }
+    return 0;
+}
+
+// The endpoint's side of the reference's non-blocking loop (mpi_perf.c:85-125)
+// on the calling thread — the full-duplex loop of include/mpx_hostlink_duplex.h;
+// c.mode and c.group are not read (both sides run the same loop), nor is
+// c.ll_max (there is no LL form) or c.skip_push (the GPU loses both
+// directions' payloads: it does all the moving).
+//   Isend i   one release store of out.ready = tx_seq0 + i + 1: tx holds the
+//             message, the GPU's pulling workgroups load it and answer with
+//             in.credit[w] (on their publish schedule);
+//   Irecv i   rx itself: the GPU's pushing workgroups store their chunks and
+//             publish in.flag[w] (on theirs);
+//   Waitall   at window slot 255 over the sends and receives of slots 0..254,
+//             and over what is in flight after the loop; slot 255 of each
+//             full window is never waited for, so recv_done = iters - iters / 256.
+// The call returns only once every one of its sends was pulled (every credit)
+// and every payload is in (every flag): rx and tx are quiet then.
+//   Check mode: every payload is checksummed in order as it lands, the
+// uncounted ones too; every one but the last is poisoned, and then out.credit
+// [gpu][0] says so — the GPU stores push i + 1 only after that (a one-slot
+// ring: all receives share rx).  Every wait services landed receives while it
+// waits, so neither side starves the other; a serviced receive restarts the
+// wait's deadline.
+// Returns 0, or 1 after a wait that ran out (r->timed_out, r->where).
+inline int run_duplex(const Call& c, Result* r) {
+    using namespace detail;
+    *r = Result{};
+    const uint64_t* flag = c.mb->in.flag[c.gpu];
+    const uint64_t* credit = c.mb->in.credit[c.gpu];
+    int next = 0;   // check mode: the next receive to check
+    auto landed = [&](uint64_t seq) {
+        for (int k = 0; k < c.nwg; ++k)
+            if (ld_acq(&flag[k]) < seq) return false;
+        return true;
+    };
+    auto pulled = [&](uint64_t seq) {
+        for (int k = 0; k < c.nwg; ++k)
+            if (ld_acq(&credit[k]) < seq) return false;
+        return true;
+    };
+    auto service = [&]() {
+        bool any = false;
+        while (c.check && next < c.iters && landed(c.rx_seq0 + (uint64_t)next + 1)) {
+            const uint64_t got = checksum(c.rx, (size_t)c.len);
+            if (next % 256 != 255) r->recv_digest += got;   // the counted receives
+            ++r->check_iters;
+            if (got != c.expect) ++r->check_failures;
+            if (next + 1 != c.iters) poison(c.rx, (size_t)c.len, next, false);   // the last payload stays
+            st_rel(&c.mb->out.credit[c.gpu][0], c.rx_seq0 + (uint64_t)next + 1);
+            ++next;
+            any = true;
+        }
+        return any;
+    };
+    // Waitall over the first `upto` sends and receives of the call
+    auto waitall = [&](int upto) {
+        const uint64_t txs = c.tx_seq0 + (uint64_t)upto, rxs = c.rx_seq0 + (uint64_t)upto;
+        auto done = [&] { return pulled(txs) && (c.check ? next >= upto : landed(rxs)); };
+        double t0 = now_s();
+        for (unsigned spins = 1;; ++spins) {
+            if (service()) t0 = now_s();
+            if (done()) return true;
+            if ((spins & 255) == 0 && now_s() - t0 > c.timeout_s) return done();
+            cpu_pause();
+        }
+    };
+    // this call's receives are posted; nothing is pushed from here (the GPU
+    // pulls this side's sends, and only inside its own call), so the peer's
+    // post is not waited for
+    st_rel(&c.mb->out.posted[c.gpu], c.call);
+    int inflight = 0;
+    for (int i = 0; i < c.iters; ++i) {
+        st_rel(&c.mb->out.ready[c.gpu], c.tx_seq0 + (uint64_t)i + 1);   // Isend; the Irecv is rx
+        service();
+        if (inflight == 255) {                          // Waitall(255): iterations i-255 .. i-1
+            if (!waitall(i)) {
+                r->timed_out = 1;
+                r->where = i;
+                return 1;
+            }
+            r->recv_done += (uint64_t)inflight;
+            inflight = 0;
+        } else {
+            ++inflight;
+        }
+    }
+    // Waitall(inflight) — and the pending slot 255 of a last full window too:
+    // counted it is not, but its send must be complete and its payload in
+    if (c.iters > 0 && !waitall(c.iters)) {
+        r->timed_out = 1;
+        r->where = c.iters - 1;
+        return 1;
+    }
+    r->recv_done += (uint64_t)inflight;
     return 0;
 }
 

@@ -31,7 +31,7 @@ constexpr int kStageMaxBytes = 60 << 10; // LDS-staged tx chunk per workgroup, m
 // Protocol ids reported in mpx_timing.protocol
 enum Proto { kProtoLL = 0, kProtoBulk = 1, kProtoSdma = 2, kProtoRccl = 3, kProtoCopy = 4, kProtoCopySteps = 5,
              kProtoCopyPipe = 6, kProtoPull = 7, kProtoSdmaPull = 8, kProtoFan = 9, kProtoFanLL = 10, kProtoHostLL = 11,
-             kProtoHostBulk = 12 };
+             kProtoHostBulk = 12, kProtoHostDuplex = 13 };
 
 // One rank's receive mailbox, in that rank's HBM (uncached / fine-grained so a
 // poll sees stores that arrive over xGMI).  Written ONLY by the peers, polled
@@ -139,9 +139,15 @@ constexpr u64 kGoCancel = 1ull << 63;
 //   [10] host link: receives of this call workgroup 0 has seen arrive in host
 //        memory, republished for the other workgroups; reset by the call's end
 //   [11] host link: 1 once workgroup 0 has seen the endpoint's post; likewise
+//   [12] full-duplex host link, check mode: the endpoint's credit word (the last
+//        of this rank's pushes it has checked) as the pushing half's reader saw
+//        it; in that call [10] holds the endpoint's ready word the same way;
+//        both reset by the call's end
+//   [13] full-duplex host link: chunks of this call's pushes drained (all
+//        pushes, all pushing workgroups), as [3] counts the pulls; likewise
 constexpr int kScratchWords = 16;
 constexpr int kScrBar = 0, kScrAbort = 1, kScrFin = 2, kScrLanded = 3, kScrSeqBase = 4, kScrLink = 6, kScrGo = 8,
-              kScrReady = 9, kScrHostSeen = 10, kScrHostPosted = 11;
+              kScrReady = 9, kScrHostSeen = 10, kScrHostPosted = 11, kScrHostCredit = 12, kScrHostSent = 13;
 
 // Non-blocking check mode ("ring"): receive j of a call with `iters`
 // iterations lands in slot (iters-1-j) mod S of the receiver, where slot 0 is
@@ -375,6 +381,10 @@ hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s);
 // the host link's kernel (k_xfer_hostlink): ping-pong and unidir only; my_mb /
 // peer_mb are the endpoint's out / in boxes, my_slot = peer_slot = this rank
 hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s);
+// the host link's full-duplex kernel (k_hostlink_duplex): the non-blocking
+// loop on a split grid of 2 * a.nwg workgroups; the same boxes and slots
+constexpr int kDuplexMaxWG = kMaxPushWG / 2;   // per direction
+hipError_t launch_hostlink_duplex(const XferArgs& a, hipStream_t s);
 hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out);
 // all `iters` copies in one launch with a grid barrier between steps; *bar
 // must be 0 at launch

@@ -483,6 +483,11 @@ struct Loop {
     mutable u64 ts[4] = {0, 0, 0, 0};   // workgroup 0's phase stamps (stamp)
     mutable u64 rdone = 0, rdig = 0;    // workgroup 0, thread 0: the call's receive
                                         // count and digest (finish_last writes them)
+    // ANYWG: the workgroup's index within its link or direction, the w of its
+    // chunk, flag and credit words (k_hostlink_duplex: blockIdx.x less the
+    // pushing half of the grid); a pair's is blockIdx.x itself
+    int wg_ = 0;
+    __device__ unsigned wg() const { return ANYWG ? (unsigned)wg_ : blockIdx.x; }
 
     __device__ void preload_ll(long long n) {
 #pragma unroll
@@ -543,7 +548,7 @@ struct Loop {
     // this workgroup's chunk [lo, hi) of a bulk push of n bytes
     __device__ void chunk_of(long long n, long long* lo, long long* hi) const {
         const long long chunk = (((n + a.nwg - 1) / a.nwg) + 15) & ~15ll;
-        *lo = (long long)blockIdx.x * chunk;
+        *lo = (long long)wg() * chunk;
         *hi = *lo + chunk < n ? *lo + chunk : n;
     }
 
@@ -589,7 +594,7 @@ struct Loop {
     // MPX_TEST_SKIP_PUSH): no payload stores, the flag is still published.
     __device__ void push_bulk(long long n, u64 seq, bool publish = true, unsigned char* dst_base = nullptr,
                               bool skip = false) const {
-        const int w = blockIdx.x;
+        const int w = wg();
         if (w >= a.nwg) return;
         long long lo, hi;
         chunk_of(n, &lo, &hi);
@@ -780,7 +785,7 @@ struct Loop {
                     drain_stores();   // the poison lands before the next payload's unpack
                 }
             }
-        } else if ((int)blockIdx.x < a.nwg) {
+        } else if ((int)wg() < a.nwg) {
             acc = sum_chunk(a.rx, n, poison, last);
         }
         const u64 s = block_sum(acc, lds4);
@@ -1185,7 +1190,7 @@ struct Loop {
         drain_stores();                                // loads and stores of every wave
         __syncthreads();
         if (threadIdx.x == 0) {
-            st_sys(&a.peer_mb->credit[a.my_slot][blockIdx.x], seq);
+            st_sys(&a.peer_mb->credit[a.my_slot][wg()], seq);
             __hip_atomic_fetch_add(&a.gbar[kScrLanded], publish, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         }
         return true;
@@ -1748,6 +1753,157 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// k_hostlink_duplex: a GPU rank's side of the non-blocking loop (mpi_perf.c:
+// 85-125) with a CPU endpoint (mpx_xfer_hostlink_duplex; the endpoint's side
+// is mpx_hostlink.h's run_duplex()) — both directions of the PCIe link loaded
+// at once.  The boxes, slots and buffers are k_xfer_hostlink's.
+//   Grid: 2 * a.nwg workgroups.  The first a.nwg PUSH (Isend i: chunk w of tx
+// into the endpoint's rx, Loop::push_bulk with the non-blocking loop's
+// deferred publish), the other a.nwg PULL (Irecv i: chunk w of the endpoint's
+// tx into rx once its ready word covers push i, Loop::pull_recv with deferred
+// publish).  Posted stores and link-crossing loads so come from different
+// workgroups and neither half waits for the other, except where the
+// reference's loop does: at the window flush and at the end.  Loop's ANYWG
+// form maps a workgroup to its chunk (wg_ = its index within its half).
+//   Who reads host memory: one workgroup per direction, the first of each
+// half.  The pushing half's polls the endpoint's post and, in check mode, its
+// credit word; the pulling half's its ready word.  Each republishes what it
+// saw in a device scratch word (kScrHostPosted, kScrHostCredit, kScrHostSeen:
+// the word's value as read) for the rest of its half, and every workgroup
+// keeps the highest value it has seen in LDS: an endpoint that has posted a
+// whole window is polled once, not 256 times.
+//   Window: at slot 255 no workgroup starts iteration i + 1 before this
+// side's receives of slots 0..254 have landed (kScrLanded, counted by the
+// pulling half at its publish points: every nb_publish receives, at slot 254
+// and at the last) and its sends of slots 0..254 are drained — a device-scope
+// counter of its own (kScrHostSent, counted by the pushing half at its
+// publish points), not the grid barrier: a workgroup that is ahead adds and
+// goes on, only the flush itself waits.  Slot 255 is waited for by nobody
+// before the end.  The end is last_to_finish: every push drained, every pull
+// landed and credited.
+//   Check mode: the pulling half checksums and poisons its chunk inside
+// pull_recv (rx is only ever written by this kernel).  The endpoint receives
+// into ONE rx, so push i + 1 is stored only after the endpoint has checked
+// and poisoned payload i and said so in its out.credit word (a one-slot
+// ring), and every push is published.
+//   Workgroup 0 counts the receives the reference's Waitall calls return
+// (iters - iters / 256) and digests their checksums, as k_xfer_pull's
+// non-blocking end does.  Every wait is bounded (should_stop / give_up).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock, 4) void k_hostlink_duplex(XferArgs a) {
+    // statics of 48 bytes: the dynamic region (the staged tx chunk) stays 16-byte aligned
+    __shared__ __attribute__((aligned(16))) u64 s_w[6];   // block_sum's four, s_seen, s_abort
+    extern __shared__ v4u s_tx[];
+    int* s_abort = reinterpret_cast<int*>(&s_w[5]);
+    if (threadIdx.x == 0) {
+        *s_abort = 0;
+        s_w[4] = 0;
+    }
+    __syncthreads();
+    Loop<MPX_MODE_NONBLOCKING, true> L{a, s_abort, s_w, s_tx, {}, &s_w[4]};
+    const bool pusher = (int)blockIdx.x < a.nwg;
+    L.wg_ = pusher ? (int)blockIdx.x : (int)blockIdx.x - a.nwg;
+    const bool reader = L.wg_ == 0;   // this half's reader of host memory
+    L.stamp(kTsEntry);
+    const long long n = a.len;
+    const u64 nw = (u64)a.nwg;
+    // Wait until the endpoint's word *host covers `want`.  The half's reader
+    // polls it across the link and republishes the value in scratch word
+    // `word`; the others poll that.  s_w[4]: the highest value seen so far.
+    auto await = [&](const u64* host, int word, u64 want, int iter) -> bool {
+        if (threadIdx.x == 0 && s_w[4] < want) {
+            const u64 t0 = now_ticks();
+            u64 spins = 0;
+            for (;;) {
+                const u64 v = reader ? ld_sys(host)
+                                     : __hip_atomic_load(&a.gbar[word], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (v >= want) {
+                    s_w[4] = v;
+                    if (reader && a.nwg > 1)
+                        __hip_atomic_store(&a.gbar[word], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    break;
+                }
+                if (L.should_stop(++spins, t0)) { L.give_up(iter); break; }
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
+        __syncthreads();
+        return !L.aborted();
+    };
+    L.post_receives();
+    bool ok = true;
+    if (pusher && a.iters > 0) {
+        // no byte of this call lands in the endpoint's rx before it has entered the call
+        if (reader) {
+            ok = L.template poll_ge<true>(&a.my_mb->posted[a.peer_slot], a.call, 0);
+            if (ok && threadIdx.x == 0 && a.nwg > 1)
+                __hip_atomic_store(&a.gbar[kScrHostPosted], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            ok = L.template poll_ge<false>(&a.gbar[kScrHostPosted], 1, 0);
+        }
+        L.stamp(kTsPosted);
+    }
+    int inflight = 0;
+    u64 pending = 0;   // this workgroup's pushes / pulls since its last publish
+    for (int i = 0; ok && i < a.iters; ++i) {
+        const int slot = i % kNbWindow;
+        const bool last = i + 1 == a.iters;
+        const bool pub = (i + 1) % a.nb_publish == 0 || slot == kNbWindow - 2 || last;
+        ++pending;
+        if (pusher) {                                  // Isend(tx, B)
+            // check mode: the endpoint has checked and poisoned payload i - 1
+            if (a.check && i > 0 && !await(&a.my_mb->credit[a.peer_slot][0], kScrHostCredit, a.tx_seq0 + (u64)i, i)) {
+                ok = false;
+                break;
+            }
+            const bool publish = pub || a.check;
+            L.push_bulk(n, a.tx_seq0 + (u64)i + 1, publish, nullptr, a.skip_push == i + 1);
+            if (publish) {                             // (drained: push_bulk)
+                if (threadIdx.x == 0)
+                    __hip_atomic_fetch_add(&a.gbar[kScrHostSent], pending, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                pending = 0;
+            }
+        } else {                                       // Irecv(rx, B)
+            const u64 seq = a.rx_seq0 + (u64)i + 1;
+            ok = await(&a.my_mb->ready[a.peer_slot], kScrHostSeen, seq, i) && L.pull_recv(n, seq, i, pub ? pending : 0);
+            if (pub) pending = 0;
+            if (!ok) break;
+        }
+        if (inflight == kNbWindow - 1) {
+            // Waitall(255, ...): the receives and the sends of slots 0..254
+            // (iterations i-255 .. i-1), every workgroup of both halves
+            ok = L.template poll_ge<false>(&a.gbar[kScrLanded], nw * (u64)i, i) &&
+                 L.template poll_ge<false>(&a.gbar[kScrHostSent], nw * (u64)i, i);
+            inflight = 0;
+        } else {
+            ++inflight;
+        }
+        if (i == 0) L.stamp(kTsFirst);
+    }
+    L.stamp(kTsLoop);
+    // Waitall(inflight): every workgroup's pushes are drained and its pulls
+    // landed and credited once it is here, so the last to finish ends the call
+    if (!L.last_to_finish()) return;
+    const bool whole = !__hip_atomic_load(&a.gbar[kScrAbort], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    u64 part = 0;
+    if (whole && a.check) {
+        const u64 fmix = mix64((u64)n);
+        for (int j = threadIdx.x; j < a.iters; j += kBlock)
+            if (j % kNbWindow != kNbWindow - 1)
+                part += __hip_atomic_load(&a.csum[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ^ fmix;
+    }
+    const u64 s = block_sum(part, s_w);
+    if (threadIdx.x == 0) {
+        L.rdone = whole ? (u64)(a.iters - a.iters / kNbWindow) : 0;
+        L.rdig = s;
+        // every other workgroup is done with the relay words and the sent count
+        for (int k = kScrHostSeen; k <= kScrHostSent; ++k)
+            __hip_atomic_store(&a.gbar[k], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    L.finish_last();
+}
+
+// ---------------------------------------------------------------------------
 // k_xfer_fan: one rank's side of a fan exchange (mpx_xfer_fan) — a block to
 // and from each of several peers in ONE launch.  The grid is the sum of the
 // links' widths; workgroup (k, w) (FanTable.map) owns chunk w of link k and
@@ -2135,6 +2291,16 @@ hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s) {
         default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), (unsigned)a.stage, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_hostlink_duplex(const XferArgs& a, hipStream_t s) {
+    // the kernel indexes flag / credit words by workgroup, and its window arithmetic divides by nb_publish
+    if (a.nwg < 1 || a.nwg > kDuplexMaxWG || a.len < 0 || a.iters < 0 || a.stage < 0 || a.stage > kStageMaxBytes ||
+        a.nb_publish < 1 || kNbWindow % a.nb_publish != 0)
+        return hipErrorInvalidValue;
+    (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
+    hipLaunchKernelGGL(k_hostlink_duplex, dim3(2u * (unsigned)a.nwg), dim3(kBlock), (unsigned)a.stage, s, a);
     return hipGetLastError();
 }
 

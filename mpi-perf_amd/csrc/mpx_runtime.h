@@ -278,6 +278,8 @@ int disarm(Rank& me);
 // k_xfer_hostlink and completes the call as a pair call's
 int run_hostlink_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, int grid, bool ll, double t_call,
                         mpx_timing* t);
+// the same with k_hostlink_duplex (mpx_xfer_hostlink_duplex): a grid of 2 * a.nwg
+int run_hostlink_duplex_kernel(Rank& me, int my_rank, int host_rank, XferArgs& a, double t_call, mpx_timing* t);
 
 // ---- mpx_engine_hostlink.hip: the host link ----------------------------------
 void free_host_endpoint(Rank& rk);   // mpx_finalize: a host endpoint's pinned memory

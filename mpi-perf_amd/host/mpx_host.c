@@ -74,7 +74,8 @@ void mpxh_print_usage(FILE *f)
 		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n\
 		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n\
 		    -H <1|2: each of the -w ranks is a GPU rank paired with a CPU endpoint across the host link;>\n\
-		       <1: the GPU rank sends first (-u 1: device to host), 2: the endpoint does (kernel engine, threads)>\n");
+		       <1: the GPU rank sends first (-u 1: device to host), 2: the endpoint does (kernel engine, threads)>\n\
+		    -X <1: with -H, every run is the full-duplex non-blocking loop across the host link (both directions at once)>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -83,7 +84,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -120,6 +121,10 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
         case 'H':
             if (strcmp(optarg, "1") && strcmp(optarg, "2")) return MPXH_PARSE_BAD_VALUE;
             o->hostlink = atoi(optarg);
+            break;
+        case 'X':
+            if (strcmp(optarg, "0") && strcmp(optarg, "1")) return MPXH_PARSE_BAD_DUPLEX;
+            o->duplex = atoi(optarg);
             break;
         case 'L': {
             char *end = NULL;
@@ -253,8 +258,53 @@ static int validate_hostlink(const mpxh_options *o, int world, FILE *err)
 
 /* mpi_perf.c:399-403; first the rules of the new flags that need two of
    them: -L traces the kernel engine's blocking loops only, -m 1 and -H (above) */
+/* -X 1 (the host link's full-duplex loop): a -H run, and nothing that says
+   which loop to run beside it.  Each refusal has a line of its own; -H's own
+   rules (validate_hostlink) cover what is left. */
+static int validate_duplex(const mpxh_options *o, FILE *err)
+{
+    if (!o->hostlink) {
+        fprintf(err, "invalid -X 1 without -H 1|2: the full-duplex loop runs between a GPU rank and its host endpoint\n");
+        return 1;
+    }
+    if (o->nonblocking) {
+        fprintf(err, "invalid -X 1 with -x 1: -X 1 alone selects the non-blocking loop on the host link\n");
+        return 1;
+    }
+    if (o->uni_dir) {
+        fprintf(err, "invalid -X 1 with -u 1: the full-duplex loop loads both directions\n");
+        return 1;
+    }
+    if (o->all_pairs) {
+        fprintf(err, "invalid -X 1 with -a 1: every GPU rank is paired with a host endpoint of its own\n");
+        return 1;
+    }
+    if (o->fan) {
+        fprintf(err, "invalid -X 1 with -m %d: a fan run has no host endpoints\n", o->fan);
+        return 1;
+    }
+    if (o->arm_set && o->arm) {
+        fprintf(err, "invalid -X 1 with -A 1: a host-link call cannot be armed ahead of the barrier\n");
+        return 1;
+    }
+    if (o->lat_cap >= 0) {
+        fprintf(err, "invalid -X 1 with -L %d: host-link calls are never traced by the latency recorder\n", o->lat_cap);
+        return 1;
+    }
+    if (o->use_dotnet) {
+        fprintf(err, "invalid -X 1 with -d 1: the .NET launcher lines describe pairs of ranks\n");
+        return 1;
+    }
+    if (o->engine != 0) {
+        fprintf(err, "invalid -X 1 with -e sdma|rccl: the host link runs on the kernel engine only\n");
+        return 1;
+    }
+    return 0;
+}
+
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
+    if (o->duplex && validate_duplex(o, err)) return 1;
     if (o->hostlink) {
         if (validate_hostlink(o, world, err)) return 1;
         world *= 2; /* the job: the GPU ranks and their endpoints */

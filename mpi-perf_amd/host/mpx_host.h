@@ -62,6 +62,11 @@ typedef struct mpxh_options {
                                            group 1 (sends first), 2 = group 0 */
     int procs;                      /* set by the host before mpxh_validate: 1 =
                                            one process per rank (a launcher)  */
+    int duplex;                     /* -X  1: with -H, every run is the
+                                           full-duplex non-blocking loop across
+                                           the host link
+                                           (mpx_xfer_hostlink_duplex /
+                                           mpx_host_xfer_duplex)              */
 } mpxh_options;
 
 /* parse status */
@@ -69,14 +74,15 @@ enum {
     MPXH_PARSE_OK = 0,
     MPXH_PARSE_USAGE = 1,           /* unknown flag / -h: usage + abort      */
     MPXH_PARSE_BAD_VALUE = 2,       /* a value of a new flag is malformed    */
-    MPXH_PARSE_CRASH = 3            /* the reference dereferences a missing
+    MPXH_PARSE_CRASH = 3,           /* the reference dereferences a missing
                                        argument (Windows variant)           */
+    MPXH_PARSE_BAD_DUPLEX = 4       /* -X with a value other than 0 or 1     */
 };
 
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:m:P:H:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:P:H:X:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);

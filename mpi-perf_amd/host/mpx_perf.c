@@ -29,7 +29,10 @@
  * mode, kernel engine) each of the -w ranks is a GPU rank paired with a CPU
  * endpoint of its own across the host link (rank world + r, its loop on a
  * thread of its own: mpx_xfer_hostlink / mpx_host_xfer); the job is then
- * those 2 * w ranks, the GPU ranks group 1 (-H 1) or group 0 (-H 2).
+ * those 2 * w ranks, the GPU ranks group 1 (-H 1) or group 0 (-H 2).  With
+ * -X 1 beside -H every run is the full-duplex non-blocking loop on that link
+ * (mpx_xfer_hostlink_duplex / mpx_host_xfer_duplex); -H still says which side
+ * is group 1 in the records.
  *
  * Built with -DMPX_WINDOWS_CLI (bin/mpx_perf_win), the front end is the
  * Windows / MS-MPI variant's (/root/reference/windows/mpi-perf.cpp):
@@ -314,7 +317,7 @@ static void note_rccl_build(void)
 static int xfer_mode(void)
 {
     if (opt.uni_dir) return MPX_MODE_UNIDIR;
-    return opt.nonblocking ? MPX_MODE_NONBLOCKING : MPX_MODE_PINGPONG;
+    return (opt.nonblocking || opt.duplex) ? MPX_MODE_NONBLOCKING : MPX_MODE_PINGPONG;
 }
 
 /* one lat-*.csv line: a recorded run's distribution (-L: the rank's; -m 2 -P:
@@ -435,6 +438,9 @@ static void *rank_main(void *arg)
                 char line[512];
                 mpxh_format_dotnet(line, sizeof line, group, r, peer, ip_of[peer], ip_of[r], B, opt.iters, opt.ppn);
                 fputs(line, stderr);
+            } else if (opt.duplex) { /* -H -X 1: the full-duplex loop, both sides alike */
+                if (is_endpoint(r)) MPX_CHECK(mpx_host_xfer_duplex(ctx, r, peer, opt.iters, B, &xo, &tm));
+                else MPX_CHECK(mpx_xfer_hostlink_duplex(ctx, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
             } else if (is_endpoint(r)) { /* -H: the endpoint's side, on this thread */
                 MPX_CHECK(mpx_host_xfer(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo, &tm));
             } else if (opt.hostlink) {
@@ -466,6 +472,7 @@ static void *rank_main(void *arg)
                             (tm.protocol >= 0 && tm.protocol <= 9) ? proto[tm.protocol]
                             : tm.protocol == 11                    ? "host_ll"
                             : tm.protocol == 12                    ? "host_bulk"
+                            : tm.protocol == 13                    ? "host_duplex"
                                                                    : "?",
                             tm.nwg,
                             (unsigned long long)tm.check_iters, tm.check_failures, run_idx,
@@ -721,6 +728,13 @@ int main(int argc, char **argv)
     if (pst == MPXH_PARSE_CRASH) raise(SIGSEGV); /* strncpy(..., argv[argc] == NULL), windows/mpi-perf.cpp:189 */
     if (pst == MPXH_PARSE_USAGE) {
         if (is_root()) mpxh_print_usage(stderr);
+        mpx_abort();
+    }
+    if (pst == MPXH_PARSE_BAD_DUPLEX) {
+        if (is_root()) {
+            fprintf(stderr, "bad value for -X (0 or 1)\n");
+            mpxh_print_usage(stderr);
+        }
         mpx_abort();
     }
     if (pst == MPXH_PARSE_BAD_VALUE) {

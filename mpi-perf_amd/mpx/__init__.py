@@ -36,6 +36,7 @@ FAN_LL_MAX = 4096    # MPX_FAN_LL_MAX: its largest block_len
 PROTO_FAN_LL = 10    # mpx_timing.protocol of such a call
 PROTO_HOSTLINK_LL = 11     # a host-link call (xfer_hostlink / host_xfer) with LL granules
 PROTO_HOSTLINK_BULK = 12   # a host-link call above the LL threshold
+PROTO_HOSTLINK_DUPLEX = 13  # the host link's full-duplex loop (xfer_hostlink_duplex / host_xfer_duplex)
 HOSTLINK_HEADER_PATH = os.path.join(PKG_ROOT, "csrc", "mpx_hostlink.h")
 ABI_VERSION = 7
 PATTERN_SEED = 0x6D70695F70657266
@@ -240,6 +241,10 @@ _SIGS = {
                                     C.c_int, C.POINTER(XferOpts), C.POINTER(Timing)]),
     "mpx_host_xfer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(XferOpts),
                                 C.POINTER(Timing)]),
+    "mpx_xfer_hostlink_duplex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.POINTER(XferOpts), C.POINTER(Timing)]),
+    "mpx_host_xfer_duplex": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(XferOpts),
+                                       C.POINTER(Timing)]),
     "mpx_host_checksum": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "mpx_hostlink_ll_max": (C.c_int, []),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
@@ -508,6 +513,36 @@ class Context:
         st = self.L.mpx_host_xfer(self.h, mode, group, host_rank, peer_rank, iters, length, C.byref(o), C.byref(t))
         if st != OK:
             e = MpxError(st, "mpx_host_xfer")
+            e.timing = t
+            raise e
+        return t
+
+    # host link, the full-duplex non-blocking loop (include/mpx_hostlink_duplex.h)
+    def xfer_hostlink_duplex(self, my_rank: int, host_rank: int, iters: int, tx: Buffer, rx: Buffer, length: int,
+                             check_payload: bool = False, expect: int = 0, timeout_ms: int = 0, nwg: int = 0,
+                             stage: bool = True) -> Timing:
+        """mpx_xfer_hostlink_duplex: GPU rank my_rank's side of the non-blocking
+        loop with host endpoint host_rank (nwg: per direction).  A failing
+        call raises MpxError carrying .timing"""
+        o = self._hostlink_opts(check_payload, expect, 0, timeout_ms, nwg, stage)
+        t = Timing()
+        st = self.L.mpx_xfer_hostlink_duplex(self.h, my_rank, host_rank, iters, C.c_void_p(tx.ptr), C.c_void_p(rx.ptr),
+                                             length, C.byref(o), C.byref(t))
+        if st != OK:
+            e = MpxError(st, "mpx_xfer_hostlink_duplex")
+            e.timing = t
+            raise e
+        return t
+
+    def host_xfer_duplex(self, host_rank: int, peer_rank: int, iters: int, length: int, check_payload: bool = False,
+                         expect: int = 0, timeout_ms: int = 0, nwg: int = 0) -> Timing:
+        """mpx_host_xfer_duplex: host endpoint host_rank's side of the same
+        loop, on the calling thread (ctypes releases the GIL for the call)"""
+        o = self._hostlink_opts(check_payload, expect, 0, timeout_ms, nwg, True)
+        t = Timing()
+        st = self.L.mpx_host_xfer_duplex(self.h, host_rank, peer_rank, iters, length, C.byref(o), C.byref(t))
+        if st != OK:
+            e = MpxError(st, "mpx_host_xfer_duplex")
             e.timing = t
             raise e
         return t

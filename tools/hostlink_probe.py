@@ -27,6 +27,27 @@ crosses PCIe between HBM and pinned host memory.  One JSON line per item:
 No pass mark; nothing here is asserted anywhere.
 
     python tools/hostlink_probe.py > profiles/hostlink.jsonl
+
+--duplex measures the full-duplex loop instead (include/mpx_hostlink_duplex.h)
+and APPENDS its lines to profiles/hostlink_duplex.jsonl (--out), all from one
+process, so the figures stand beside each other's:
+
+    duplex            the non-blocking loop at 4 MiB x 50 iterations, best and
+                      median of 3 calls after a warm-up, at per-direction
+                      widths 1 ... 64 and at the default width; aggregate GB/s
+                      = 2 * B * iters / the kernel's own clock (posted wait
+                      excluded), per direction half of it (both directions
+                      move the same bytes in the same span), and as a fraction
+                      of 2 x 63 GB/s.
+    unidir            the two one-direction figures at the default width, the
+                      same bytes, iterations and clock.
+    duplex_reference  two concurrent hipMemcpyAsync streams between the same
+                      buffers, one per direction, 50 copies each and one
+                      synchronise of each under a host clock: the runtime's own
+                      full-duplex figure; and each stream alone.
+    numa              as above.
+
+    python tools/hostlink_probe.py --duplex
 """
 import argparse
 import ctypes as C
@@ -41,6 +62,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=5)
 ap.add_argument("--bw-bytes", type=int, default=4 << 20)
 ap.add_argument("--bw-iters", type=int, default=50)
+ap.add_argument("--duplex", action="store_true", help="measure the full-duplex loop; appends to --out")
+ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                              "hostlink_duplex.jsonl"))
 args = ap.parse_args()
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-perf_amd"))
 import mpx  # noqa: E402
@@ -55,6 +79,9 @@ os.environ.pop("MPX_HOSTLINK_WG", None)
 hip = C.CDLL("libamdhip64.so.7")
 hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
 hip.hipDeviceSynchronize.argtypes = []
+hip.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+hip.hipStreamSynchronize.argtypes = [C.c_void_p]
+hip.hipStreamDestroy.argtypes = [C.c_void_p]
 libc = C.CDLL(None, use_errno=True)
 
 c = mpx.Context(2, "kernel")
@@ -95,10 +122,145 @@ def call(mode, gpu_group, n, iters, nwg=0):
     return ph["kernel_s"] - ph["posted_wait_s"], out[G], out[E]
 
 
+def call_duplex(n, iters, nwg=0):
+    """one full-duplex call, both sides; (the GPU side's loop seconds on the kernel's clock, its Timing, the endpoint's)"""
+    out, errs = {}, []
+    bar = threading.Barrier(2)
+
+    def side(r):
+        try:
+            cpu_of[r] = libc.sched_getcpu()
+            bar.wait()
+            if r == G:
+                out[r] = c.xfer_hostlink_duplex(G, E, iters, gtx, grx, n, timeout_ms=20000, nwg=nwg)
+            else:
+                out[r] = c.host_xfer_duplex(E, G, iters, n, timeout_ms=20000, nwg=nwg)
+        except Exception as e:  # noqa: BLE001
+            errs.append(f"rank {r}: {e}")
+            bar.abort()
+    th = [threading.Thread(target=side, args=(r,)) for r in (G, E)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    if errs:
+        raise RuntimeError("; ".join(errs))
+    ph = c.phases(G)
+    return ph["kernel_s"] - ph["posted_wait_s"], out[G], out[E]
+
+
 def spread(v, scale, digits=3):
     return dict(median=round(statistics.median(v) * scale, digits), min=round(min(v) * scale, digits),
                 max=round(max(v) * scale, digits))
 
+
+# ---- NUMA ---------------------------------------------------------------------
+
+
+def node_of_cpu(cpu):
+    for d in glob.glob("/sys/devices/system/node/node[0-9]*"):
+        for part in open(os.path.join(d, "cpulist")).read().strip().split(","):
+            lo, _, hi = part.partition("-")
+            if part and int(lo) <= cpu <= int(hi or lo):
+                return int(d.rsplit("node", 1)[1])
+    return None
+
+
+def node_of_page(addr):
+    """move_pages(2) with no target nodes: the node each page is on"""
+    page = C.c_void_p(addr & ~4095)
+    status = C.c_int(-1)
+    rc = libc.syscall(279, 0, C.c_ulong(1), C.byref(page), None, C.byref(status), 0)
+    return status.value if rc == 0 else None
+
+
+# ---- the full-duplex loop (--duplex) ---------------------------------------------
+def duplex_probe():
+    import time
+    B, IT = args.bw_bytes, args.bw_iters
+    lines = []
+
+    def emit(**kw):
+        lines.append(json.dumps(dict(kind=KIND, **kw)))
+        print(lines[-1], flush=True)
+
+    clock = "kernel (s_memrealtime), posted wait excluded"
+    rows = []
+    for nwg in (0, 1, 2, 4, 8, 16, 32, 64):
+        call_duplex(B, 5, nwg)
+        res = [call_duplex(B, IT, nwg) for _ in range(3)]
+        gbps = [2 * B * IT / r[0] / 1e9 for r in res]
+        assert all(r[1].recv_done == IT and r[2].recv_done == IT and r[1].protocol == 13 for r in res)
+        rows.append(dict(nwg_asked=nwg, nwg_per_direction=res[0][1].nwg, GBps_aggregate_best=round(max(gbps), 2),
+                         GBps_aggregate_median=round(statistics.median(gbps), 2),
+                         GBps_per_direction_best=round(max(gbps) / 2, 2),
+                         fraction_of_2x63GBps_spec=round(max(gbps) / (2 * PCIE_SPEC_GBPS), 3)))
+    swept = [r for r in rows if r["nwg_asked"]]
+    best = max(swept, key=lambda r: r["GBps_aggregate_median"])
+    emit(item="duplex", mode="nonblocking, full duplex", bytes=B, iters=IT, calls=3, default_width=rows[0], sweep=swept,
+         best_width=best["nwg_per_direction"], clock=clock)
+    uni = {}
+    for gpu_group, direction in ((1, "device_to_host"), (0, "host_to_device")):
+        call(mpx.MODE_UNIDIR, gpu_group, B, 5)
+        res = [call(mpx.MODE_UNIDIR, gpu_group, B, IT) for _ in range(3)]
+        gbps = [B * IT / r[0] / 1e9 for r in res]
+        uni[direction] = max(gbps)
+        emit(item="unidir", direction=direction, bytes=B, iters=IT, calls=3, nwg=res[0][1].nwg, GBps_best=round(max(gbps), 2),
+             GBps_median=round(statistics.median(gbps), 2), fraction_of_63GBps_spec=round(max(gbps) / PCIE_SPEC_GBPS, 3),
+             clock=clock)
+    emit(item="duplex_vs_unidir", default_width_aggregate_GBps=rows[0]["GBps_aggregate_best"],
+         sum_of_the_unidir_figures_GBps=round(sum(uni.values()), 2),
+         aggregate_over_sum=round(rows[0]["GBps_aggregate_best"] / sum(uni.values()), 3))
+    # the runtime's copy engines: one stream per direction, alone and together
+    st = [C.c_void_p(), C.c_void_p()]
+    for x in st:
+        assert hip.hipStreamCreateWithFlags(C.byref(x), 1) == 0          # hipStreamNonBlocking
+    copies = (("device_to_host", C.addressof(hrx), grx.ptr, 2, st[0]), ("host_to_device", gtx.ptr, C.addressof(htx), 1, st[1]))
+
+    def timed(which):
+        v = []
+        for rep in range(4):
+            hip.hipDeviceSynchronize()
+            t0 = time.perf_counter()
+            for _ in range(IT):
+                for k in which:
+                    _, dst, src, kind, stream = copies[k]
+                    rc = hip.hipMemcpyAsync(C.c_void_p(dst), C.c_void_p(src), B, kind, stream)
+                    assert rc == 0, rc
+            for k in which:
+                assert hip.hipStreamSynchronize(copies[k][4]) == 0
+            if rep:
+                v.append(len(which) * B * IT / (time.perf_counter() - t0) / 1e9)
+        return v
+    # (the host-to-device copies land in the GPU rank's tx, which is filled anew below)
+    alone = {copies[k][0]: timed([k]) for k in (0, 1)}
+    both = timed([0, 1])
+    c.fill(gtx, CAP, mpx.FILL_SPLITMIX, 11)
+    for x in st:
+        hip.hipStreamDestroy(x)
+    emit(item="duplex_reference", what="two concurrent hipMemcpyAsync streams, one per direction, the same pinned and device "
+         "buffers", bytes=B, copies_per_direction=IT, calls=3, GBps_aggregate_best=round(max(both), 2),
+         GBps_aggregate_median=round(statistics.median(both), 2),
+         fraction_of_2x63GBps_spec=round(max(both) / (2 * PCIE_SPEC_GBPS), 3),
+         alone_GBps_best={k: round(max(v), 2) for k, v in alone.items()},
+         clock="host clock around the copies and one synchronise per stream")
+    try:
+        gpu_node = int(open(f"/sys/bus/pci/devices/{mpx.bus_id(0).lower()}/numa_node").read())
+    except OSError:
+        gpu_node = None
+    emit(item="numa", binding="not controlled: no thread or allocation was bound to a node", gpu_numa_node=gpu_node,
+         endpoint_tx_node=node_of_page(C.addressof(htx)), endpoint_rx_node=node_of_page(C.addressof(hrx)),
+         gpu_side_thread=dict(cpu=cpu_of.get(G), node=node_of_cpu(cpu_of.get(G, -1))),
+         endpoint_thread=dict(cpu=cpu_of.get(E), node=node_of_cpu(cpu_of.get(E, -1))))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if args.duplex:
+    duplex_probe()
+    c.close()
+    sys.exit(0)
 
 # ---- latency ------------------------------------------------------------------
 for gpu_group in (1, 0):
@@ -166,26 +328,6 @@ for gpu_group in (1, 0):
     print(json.dumps(dict(kind=KIND, item="ll_threshold", mode="pingpong", gpu_group=gpu_group, calls=args.calls, iters=1000,
                           sweep=rows, largest_size_where_ll_is_not_slower=chosen, in_force=mpx.hostlink_ll_max())),
           flush=True)
-
-# ---- NUMA ---------------------------------------------------------------------
-
-
-def node_of_cpu(cpu):
-    for d in glob.glob("/sys/devices/system/node/node[0-9]*"):
-        for part in open(os.path.join(d, "cpulist")).read().strip().split(","):
-            lo, _, hi = part.partition("-")
-            if part and int(lo) <= cpu <= int(hi or lo):
-                return int(d.rsplit("node", 1)[1])
-    return None
-
-
-def node_of_page(addr):
-    """move_pages(2) with no target nodes: the node each page is on"""
-    page = C.c_void_p(addr & ~4095)
-    status = C.c_int(-1)
-    rc = libc.syscall(279, 0, C.c_ulong(1), C.byref(page), None, C.byref(status), 0)
-    return status.value if rc == 0 else None
-
 
 try:
     gpu_node = int(open(f"/sys/bus/pci/devices/{mpx.bus_id(0).lower()}/numa_node").read())
