@@ -511,6 +511,12 @@ int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
    contract, in a header of their own, which is part of this one. */
 #include "mpx_hostlink_duplex.h"
 
+/* ---- host link: per-iteration latency distribution, on both ends ----------- */
+/* The host-link recorder: mpx_hostlink_lat_enable / _disable / _reset / _get /
+   _raw and MPX_HOSTLINK_LAT_RAW_MAX are declared, with their contract, in a
+   header of their own, which is part of this one. */
+#include "mpx_hostlink_lat.h"
+
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of
    two [2^e, 2^(e+1)) splits into 16 equal buckets (<= 1/16 relative);

@@ -64,7 +64,8 @@
    token_by = 0 only; both ends of a link must be advanced alike).  Host-link calls are
    never traced by the latency recorder (mpx_lat_*), like non-blocking calls,
    and cannot be armed.  MPX_TEST=skip_push=k loses the k-th B-byte payload of
-   a sending side (never an LL ack).
+   a sending side (never an LL ack).  The host link has a recorder of its own,
+   on both ends: mpx_hostlink_lat.h.
    The ABI version is unchanged: callers detect the feature by symbol. */
 
 /* Make `rank` a host endpoint with tx and rx of len bytes each (len = 0: 16

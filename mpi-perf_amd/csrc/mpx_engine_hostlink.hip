@@ -77,6 +77,9 @@ void free_host_endpoint(Rank& rk) {
     if (rk.tx) (void)hipHostFree(rk.tx);
     if (rk.rx) (void)hipHostFree(rk.rx);
     if (rk.host_mb) (void)hipHostFree(rk.host_mb);
+    free(rk.host_lat);
+    rk.host_lat = nullptr;
+    rk.host_lat_on = false;
     rk.tx = rk.rx = nullptr;
     rk.host_mb = nullptr;
     rk.host = false;
@@ -198,6 +201,8 @@ int mpx_xfer_hostlink(mpx_ctx* ctx, int mode, int my_group, int my_rank, int hos
     a.check = check ? 1 : 0;
     a.ll_max = mpx_hostlink_ll_max();
     a.skip_push = test_knobs().skip_push;
+    // the host-link recorder (mpx_hostlink_lat_enable): launch_hostlink then picks the traced kernels
+    a.lat = me.hostlink_lat.on ? me.hostlink_lat.block(host_rank) : nullptr;
     const bool ll_send = send_len <= a.ll_max, ll_recv = recv_len <= a.ll_max;
     const int grid = (ll_send && ll_recv) ? 1 : a.nwg;
     // bulk pushes read tx from LDS when one workgroup's chunk fits, as a pair's
@@ -245,9 +250,14 @@ int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_
     c.call = knobs.no_posted ? 0 : me.calls[peer_rank];
     c.timeout_s = (opts && opts->timeout_ms ? opts->timeout_ms : 10000) * 1e-3;
     c.skip_push = knobs.skip_push;
+    c.lag_iter = knobs.host_lag_iter;
+    c.lag_us = knobs.host_lag_us;
+    // the endpoint's recorder (mpx_hostlink_lat_enable): the block of the GPU peer
+    if (me.host_lat_on)
+        c.lat = reinterpret_cast<hostlink::LatRec*>(me.host_lat + (size_t)peer_rank * hostlink::lat_rec_bytes(me.host_lat_cap));
     hostlink::Result r;
     const double t0 = now_s();
-    const int rc = hostlink::run(c, &r);
+    const int rc = c.lat ? hostlink::run_loop<true>(c, &r) : hostlink::run(c, &r);
     t->wall_s = now_s() - t0;
     t->device_s = 0;
     t->launches = 0;
@@ -268,6 +278,141 @@ int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_
     if (r.check_failures)
         return fail(MPX_ERR_CHECK, "host endpoint %d: %d of %llu received payloads failed the checksum", host_rank,
                     r.check_failures, (unsigned long long)r.check_iters);
+    return MPX_OK;
+}
+
+// ---- the host-link recorder (include/mpx_hostlink_lat.h) -----------------------
+// A GPU rank's blocks are a third Recorder (Rank.hostlink_lat: device memory,
+// mpx_runtime.hip's helpers); an endpoint's are hostlink::LatRec blocks in
+// ordinary host memory, read and cleared right here.
+
+namespace {
+static_assert(sizeof(hostlink::LatRec) == sizeof(LatBlock) && offsetof(hostlink::LatRec, hist) == offsetof(LatBlock, hist) &&
+                  offsetof(hostlink::LatRec, raw) == offsetof(LatBlock, raw),
+              "LatRec has the device block's layout");
+
+hostlink::LatRec* host_lat_block(const Rank& h, int i) {
+    return reinterpret_cast<hostlink::LatRec*>(h.host_lat + (size_t)i * hostlink::lat_rec_bytes(h.host_lat_cap));
+}
+void host_lat_clear(Rank& h, int blocks) {
+    for (int i = 0; i < blocks; ++i) {
+        hostlink::LatRec* b = host_lat_block(h, i);
+        memset(b, 0, offsetof(hostlink::LatRec, raw));
+        b->raw_cap = (uint64_t)h.host_lat_cap;
+    }
+}
+// The rank a host-link recorder call names: 1 = an attached local GPU rank
+// (holding no armed call), 2 = a host endpoint; else the status in *rc.
+int hostlink_lat_rank(mpx_ctx* ctx, int rank, int* rc) {
+    *rc = MPX_OK;
+    if (!ctx) {
+        *rc = fail(MPX_ERR_INVALID, "ctx is NULL");
+        return 0;
+    }
+    if (rank >= 0 && rank < ctx->nranks && ctx->r[rank].host) return 2;
+    if (rank < 0 || rank >= ctx->nranks || !ctx->r[rank].local) {
+        *rc = fail(MPX_ERR_INVALID, "rank %d is neither a local GPU rank nor a host endpoint", rank);
+        return 0;
+    }
+    if (ctx->r[rank].armed) {
+        *rc = fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", rank);
+        return 0;
+    }
+    return 1;
+}
+int hostlink_lat_peer(const mpx_ctx* ctx, int rank, int peer) {
+    if (peer < 0 || peer >= ctx->nranks || peer == rank) return fail(MPX_ERR_INVALID, "rank %d: peer rank %d", rank, peer);
+    return MPX_OK;
+}
+int hostlink_lat_off(int rank) { return fail(MPX_ERR_STATE, "rank %d: the host-link recorder is not enabled", rank); }
+}  // namespace
+
+int mpx_hostlink_lat_enable(mpx_ctx* ctx, int rank, int raw_cap) {
+    if (!ctx) return fail(MPX_ERR_INVALID, "ctx is NULL");
+    if (ctx->engine != MPX_ENGINE_KERNEL)
+        return fail(MPX_ERR_UNSUPPORTED, "the host-link recorder runs inside the kernel engine's host-link loop: not this engine");
+    int rc;
+    const int kind = hostlink_lat_rank(ctx, rank, &rc);
+    if (!kind) return rc;
+    Rank& me = ctx->r[rank];
+    if (kind == 1) return recorder_enable(me, me.hostlink_lat, ctx->nranks, raw_cap, MPX_HOSTLINK_LAT_RAW_MAX, "host-link recorder");
+    if (raw_cap < 0 || raw_cap > MPX_HOSTLINK_LAT_RAW_MAX)
+        return fail(MPX_ERR_INVALID, "raw_cap %d not in [0,%d]", raw_cap, MPX_HOSTLINK_LAT_RAW_MAX);
+    if (!me.host_lat || me.host_lat_alloc < raw_cap) {
+        const size_t bytes = (size_t)ctx->nranks * hostlink::lat_rec_bytes(raw_cap);
+        void* p = malloc(bytes);
+        if (!p) return fail(MPX_ERR_NOMEM, "host-link recorder of %zu B", bytes);
+        free(me.host_lat);
+        me.host_lat = static_cast<unsigned char*>(p);
+        me.host_lat_alloc = raw_cap;
+    }
+    me.host_lat_cap = raw_cap;
+    host_lat_clear(me, ctx->nranks);
+    me.host_lat_on = true;
+    return MPX_OK;
+}
+
+int mpx_hostlink_lat_disable(mpx_ctx* ctx, int rank) {
+    int rc;
+    const int kind = hostlink_lat_rank(ctx, rank, &rc);
+    if (!kind) return rc;
+    if (kind == 1) ctx->r[rank].hostlink_lat.on = false;   // the blocks stay until finalize
+    else ctx->r[rank].host_lat_on = false;
+    return MPX_OK;
+}
+
+int mpx_hostlink_lat_reset(mpx_ctx* ctx, int rank) {
+    int rc;
+    const int kind = hostlink_lat_rank(ctx, rank, &rc);
+    if (!kind) return rc;
+    Rank& me = ctx->r[rank];
+    if (kind == 1) return me.hostlink_lat.on ? recorder_reset(me, me.hostlink_lat) : hostlink_lat_off(rank);
+    if (!me.host_lat_on) return hostlink_lat_off(rank);
+    host_lat_clear(me, ctx->nranks);
+    return MPX_OK;
+}
+
+int mpx_hostlink_lat_get(mpx_ctx* ctx, int rank, int peer, mpx_lat* out) {
+    int rc;
+    const int kind = hostlink_lat_rank(ctx, rank, &rc);
+    if (!kind) return rc;
+    if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
+    TRY(hostlink_lat_peer(ctx, rank, peer));
+    Rank& me = ctx->r[rank];
+    if (kind == 1) return me.hostlink_lat.on ? recorder_get(me, me.hostlink_lat, peer, out) : hostlink_lat_off(rank);
+    if (!me.host_lat_on) return hostlink_lat_off(rank);
+    const hostlink::LatRec& b = *host_lat_block(me, peer);
+    memset(out, 0, sizeof *out);
+    out->count = b.count;
+    out->calls = b.calls;
+    out->min_ticks = b.min_ticks;
+    out->max_ticks = b.max_ticks;
+    out->sum_ticks = b.sum_ticks;
+    out->max_iter = b.max_iter;
+    out->last_iters = b.last_iters;
+    out->tick_s = 1e-9;   // CLOCK_MONOTONIC in nanoseconds
+    static_assert(sizeof out->hist == sizeof b.hist, "mpx_lat and LatRec histograms differ");
+    memcpy(out->hist, b.hist, sizeof b.hist);
+    return MPX_OK;
+}
+
+int mpx_hostlink_lat_raw(mpx_ctx* ctx, int rank, int peer, uint64_t* stamps, int cap, int* n) {
+    int rc;
+    const int kind = hostlink_lat_rank(ctx, rank, &rc);
+    if (!kind) return rc;
+    if (!n || cap < 0 || (!stamps && cap > 0)) return fail(MPX_ERR_INVALID, "bad argument");
+    *n = 0;
+    TRY(hostlink_lat_peer(ctx, rank, peer));
+    Rank& me = ctx->r[rank];
+    if (kind == 1) return me.hostlink_lat.on ? recorder_raw(me, me.hostlink_lat, peer, stamps, cap, n) : hostlink_lat_off(rank);
+    if (!me.host_lat_on) return hostlink_lat_off(rank);
+    const hostlink::LatRec& b = *host_lat_block(me, peer);
+    // t[0] alone says nothing: with raw_cap = 0 no stamp is reported (as a GPU rank's)
+    uint64_t have = me.host_lat_cap > 0 ? b.raw_n : 0;
+    if (have > (uint64_t)me.host_lat_cap + 1) have = (uint64_t)me.host_lat_cap + 1;
+    if (have > (uint64_t)cap) have = (uint64_t)cap;
+    if (have) memcpy(stamps, b.raw, (size_t)have * sizeof(uint64_t));
+    *n = (int)have;
     return MPX_OK;
 }
 

@@ -22,6 +22,9 @@
 #include <string.h>
 #include <time.h>
 
+// mpx_lat_bucket and MPX_LAT_BUCKETS: one definition for host and device (plain C)
+#include "../../include/mpx.h"
+
 #if defined(__x86_64__) || defined(__i386__)
 #include <immintrin.h>
 #endif
@@ -73,6 +76,11 @@ inline double now_s() {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec + (double)ts.tv_nsec * 1e-9;
+}
+inline uint64_t now_ns() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
 }
 inline uint64_t ld_acq(const uint64_t* p) { return __atomic_load_n(p, __ATOMIC_ACQUIRE); }
 inline void st_rel(uint64_t* p, uint64_t v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
@@ -129,6 +137,21 @@ inline int narrow_nwg(int w, long long len) {
     return n < 1 ? 1 : (int)n;
 }
 
+// An endpoint's latency recorder block (include/mpx_hostlink_lat.h), in
+// ordinary host memory: mpx_lat's accumulated fields, the raw_cap in force
+// and the last traced call's stamps, in CLOCK_MONOTONIC nanoseconds.  It has
+// the device block's layout (LatBlock, mpx_internal.h) and is allocated with
+// room for raw_cap + 1 stamps.  Written by the thread inside run_traced() and
+// by the caller only between that endpoint's calls.
+struct LatRec {
+    uint64_t count, calls, min_ticks, max_ticks, sum_ticks, max_iter, last_iters;
+    uint64_t raw_cap;          // iterations of a call whose end stamp is kept
+    uint64_t raw_n;            // stamps of the last traced call in raw[]: 1 + min(iters, raw_cap)
+    uint32_t hist[MPX_LAT_BUCKETS];
+    uint64_t raw[1];           // raw_cap + 1 stamps: t[0], then t[i+1] for i < raw_cap
+};
+inline size_t lat_rec_bytes(int raw_cap) { return sizeof(LatRec) + (size_t)raw_cap * sizeof(uint64_t); }
+
 // One call of the CPU endpoint.
 struct Call {
     HostMailbox* mb = nullptr;
@@ -146,6 +169,9 @@ struct Call {
     uint64_t call = 0;         // the link's call number (posted)
     double timeout_s = 10.0;   // per wait, CLOCK_MONOTONIC
     int skip_push = 0;         // test knob: 1 + the iteration whose payload is lost
+    int lag_iter = -1;         // test knob (host_lag): the iteration before whose first step
+    long long lag_us = 0;      //   the endpoint busy-waits lag_us; -1 = off
+    LatRec* lat = nullptr;     // the block of the GPU peer (run_traced); nullptr = untraced
 };
 struct Result {
     uint64_t recv_done = 0, recv_digest = 0, check_iters = 0;
@@ -216,12 +242,71 @@ inline bool send_bulk(const Call& c, const Waiter& w, uint64_t seq) {
     return true;
 }
 
+// The endpoint's per-iteration stamps, as the kernels' LatTrace takes them: the
+// deltas stream into locals (min, max, the iteration of the first maximum; the
+// sum telescopes), one add on the histogram bucket and, while i < raw_cap, one
+// store of the stamp; the fold into the block comes after the loop.
+// Trace<false> is empty: the untraced loop reads no clock for it.
+template <bool LAT>
+struct Trace {
+    void begin(LatRec*, int) {}
+    void tick(int) {}
+    void end() {}
+};
+template <>
+struct Trace<true> {
+    LatRec* blk = nullptr;
+    uint64_t prev = 0, mn = ~0ull, mx = 0;
+    uint64_t cap = 0, maxi = 0, n = 0;
+    void begin(LatRec* b, int iters) {
+        blk = b;
+        cap = (uint64_t)iters < b->raw_cap ? (uint64_t)iters : b->raw_cap;
+        prev = now_ns();
+        b->raw[0] = prev;
+    }
+    void tick(int i) {
+        const uint64_t t = now_ns();
+        const uint64_t d = t - prev;
+        prev = t;
+        if (d < mn) mn = d;
+        if (d > mx) {
+            mx = d;
+            maxi = (uint64_t)i;
+        }
+        ++n;
+        ++blk->hist[mpx_lat_bucket(d)];   // (2^32 ns and more: the last bucket)
+        if ((uint64_t)i < cap) blk->raw[i + 1] = t;
+    }
+    void end() {
+        LatRec& b = *blk;
+        if (n) {
+            if (b.count == 0 || mn < b.min_ticks) b.min_ticks = mn;
+            if (b.count == 0 || mx > b.max_ticks) {
+                b.max_ticks = mx;
+                b.max_iter = maxi;
+            }
+            b.sum_ticks += prev - b.raw[0];
+            b.count += n;
+        }
+        b.calls += 1;
+        b.last_iters = n;
+        b.raw_n = 1 + (n < cap ? n : cap);
+    }
+};
+
 }  // namespace detail
 
 // The endpoint's side of the reference's ping-pong (mpi_perf.c:66-83) or
 // unidirectional (:127-145) loop on the calling thread.  Returns 0, or 1 after
 // a wait that ran out (r->timed_out, r->where).
-inline int run(const Call& c, Result* r) {
+//   LAT: the traced form (c.lat, include/mpx_hostlink_lat.h).  t[0] is taken
+// right before the loop — out.posted is stored and, on a side that sends
+// first, the peer's post was seen — and t[i+1] when iteration i's last step
+// has returned, check and poison included: one clock_gettime per iteration.
+// A call that times out leaves the block as the loop left it (undefined until
+// reset).  LAT = false reads the clock only where its waits always did.
+template <bool LAT>
+inline int run_loop(const Call& c, Result* r) {
     using namespace detail;
     *r = Result{};
     const Waiter w{c.timeout_s};
@@ -257,16 +342,26 @@ inline int run(const Call& c, Result* r) {
         }
         return true;
     };
+    Trace<LAT> T;
+    if (LAT) T.begin(c.lat, c.iters);
     for (int i = 0; i < c.iters; ++i) {
+        if (i == c.lag_iter && c.lag_us > 0) {   // test knob (host_lag)
+            const double t0 = now_s();
+            while ((now_s() - t0) * 1e6 < (double)c.lag_us) cpu_pause();
+        }
         const bool ok = c.group == 1 ? (send(i) && recv(i)) : (recv(i) && send(i));
         if (!ok) {
             r->timed_out = 1;
             r->where = i;
             return 1;
         }
+        if (LAT) T.tick(i);
     }
+    if (LAT) T.end();
     return 0;
 }
+// the untraced entry point (mpx_host_xfer calls run_loop<true> when c.lat is set)
+inline int run(const Call& c, Result* r) { return run_loop<false>(c, r); }
 
 // The endpoint's side of the reference's non-blocking loop (mpi_perf.c:85-125)
 // on the calling thread — the full-duplex loop of include/mpx_hostlink_duplex.h;

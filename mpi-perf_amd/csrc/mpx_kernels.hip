@@ -14,6 +14,7 @@
 //   k_xfer_hostlink  a GPU rank's side of the ping-pong / unidir loop with a
 //               CPU endpoint across PCIe (mpx_xfer_hostlink): the same pushes,
 //               and bulk receives pulled from the endpoint's pinned tx
+//   k_hostlink_lat  the same loop traced per iteration (mpx_hostlink_lat_*)
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -1654,8 +1655,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull_lat(XferArgs a) {
 // with the payload loads (a supposition, not a measurement: DESIGN.md §5).
 // Grid: 1 when both directions are LL, else a.nwg; co-resident (4 per CU).
 // ---------------------------------------------------------------------------
-template <int MODE, int GROUP>
-__global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
+// LAT: the traced form (mpx_hostlink_lat_*; LatTrace, workgroup 0's lane 0)
+// into a.lat, the block of the endpoint's rank in the rank's host-link
+// recorder.  t[0] is the instant first_iter_s counts from (kTsPosted on the
+// side that pushes first, else kTsEntry); the one clock read at the bottom of
+// iteration i is t[i+1] and, for i = 0, the kTsFirst stamp.  k_xfer_hostlink
+// is the LAT = false wrapper, k_hostlink_lat the other.
+template <int MODE, int GROUP, bool LAT>
+__device__ __forceinline__ void hostlink_body(const XferArgs a) {
     static_assert(MODE == MPX_MODE_PINGPONG || MODE == MPX_MODE_UNIDIR, "the blocking loops only");
     // statics of 48 bytes: the dynamic region (the staged tx chunk) stays 16-byte aligned
     __shared__ __attribute__((aligned(16))) u64 s_w[6];   // block_sum's four, s_seen, s_abort
@@ -1681,6 +1688,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
         if (threadIdx.x == 0 && gridDim.x > 1)
             __hip_atomic_store(&a.gbar[word], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
+    LatTrace<LAT> T;
     L.post_receives();
     bool ok = true;
     if (GROUP == 1 && a.iters > 0) {
@@ -1693,6 +1701,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
         }
         L.stamp(kTsPosted);
     }
+    if constexpr (LAT) T.begin(a.lat, L.ts[kTsEntry], L.ts[kTsPosted], a.iters);
     auto send = [&](int i) {
         ++txs;
         const bool lose = sends_n && a.skip_push == i + 1;   // test knob: a B-byte payload, never an ack
@@ -1739,7 +1748,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
     for (int i = 0; ok && i < a.iters; ++i) {
         if constexpr (GROUP == 1) ok = send(i) && recv(i);   // mpi_perf.c:72-75, 135-137
         else ok = recv(i) && send(i);                        // mpi_perf.c:79-80, 141-142
-        if (i == 0) L.stamp(kTsFirst);
+        if constexpr (LAT) {                                 // one clock read: the iteration's end, and
+            if (T.on()) {                                    // for i = 0 also the kTsFirst stamp
+                const u64 t = T.tick(i);
+                if (i == 0) L.ts[kTsFirst] = t;
+            }
+        } else if (i == 0) {
+            L.stamp(kTsFirst);
+        }
     }
     L.stamp(kTsLoop);
     if (L.last_to_finish()) {
@@ -1748,8 +1764,17 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
             __hip_atomic_store(&a.gbar[kScrHostSeen], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&a.gbar[kScrHostPosted], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        if constexpr (LAT) T.end();   // (behind the finish barrier, as xfer_body folds)
         L.finish_last();
     }
+}
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
+    hostlink_body<MODE, GROUP, false>(a);
+}
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_hostlink_lat(XferArgs a) {
+    hostlink_body<MODE, GROUP, true>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -2285,9 +2310,14 @@ hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s) {
     void (*k)(XferArgs) = nullptr;
     switch (a.mode) {
         case MPX_MODE_PINGPONG:
-            k = a.group ? k_xfer_hostlink<MPX_MODE_PINGPONG, 1> : k_xfer_hostlink<MPX_MODE_PINGPONG, 0>;
+            // the host-link recorder on (a.lat): the traced instantiations
+            if (a.lat) k = a.group ? k_hostlink_lat<MPX_MODE_PINGPONG, 1> : k_hostlink_lat<MPX_MODE_PINGPONG, 0>;
+            else k = a.group ? k_xfer_hostlink<MPX_MODE_PINGPONG, 1> : k_xfer_hostlink<MPX_MODE_PINGPONG, 0>;
             break;
-        case MPX_MODE_UNIDIR: k = a.group ? k_xfer_hostlink<MPX_MODE_UNIDIR, 1> : k_xfer_hostlink<MPX_MODE_UNIDIR, 0>; break;
+        case MPX_MODE_UNIDIR:
+            if (a.lat) k = a.group ? k_hostlink_lat<MPX_MODE_UNIDIR, 1> : k_hostlink_lat<MPX_MODE_UNIDIR, 0>;
+            else k = a.group ? k_xfer_hostlink<MPX_MODE_UNIDIR, 1> : k_xfer_hostlink<MPX_MODE_UNIDIR, 0>;
+            break;
         default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), (unsigned)a.stage, s, a);

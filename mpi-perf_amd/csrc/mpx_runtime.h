@@ -185,6 +185,15 @@ struct Rank {
     Recorder lat;                  // latency recorder (mpx_lat_enable): one block; on: blocking calls are traced
     Recorder fan_lat;              // link recorder (mpx_fan_lat_enable): ctx->nranks blocks, keyed by peer
                                    //   rank; on: MPX_FAN_LL calls of this rank are traced per link
+    Recorder hostlink_lat;         // host-link recorder (mpx_hostlink_lat_enable): ctx->nranks blocks, keyed by
+                                   //   the endpoint's rank; on: this rank's mpx_xfer_hostlink calls are traced
+    // a host endpoint's host-link recorder: ctx->nranks hostlink::LatRec blocks in
+    // ordinary host memory (malloc), keyed by the GPU peer's rank, host_lat_stride
+    // apart; touched only by mpx_host_xfer's thread and, between its calls, the caller
+    unsigned char* host_lat = nullptr;
+    int host_lat_alloc = 0;        //   raw_cap the blocks were allocated for
+    int host_lat_cap = 0;          //   raw_cap in force (the blocks' stride)
+    bool host_lat_on = false;
     FanTable* fan_tab = nullptr;   // fan exchange (mpx_xfer_fan): the link table in device memory
     FanTable* fan_host = nullptr;  //   and its pinned host image (allocated on the first fan call)
     u64 tx_seq[MPX_MAX_RANKS] = {};
@@ -249,6 +258,8 @@ struct TestKnobs {
     int lag_rank = -1, lag_wg = 0;
     long long lag_us = 0;
     bool no_posted = false, no_pull_wait = false;
+    int host_lag_iter = -1;        // host_lag=<iter>:<us>: a host endpoint stalls before that iteration
+    long long host_lag_us = 0;
     int fail_launch = -1;
     bool fail_copy = false;
 };
@@ -258,6 +269,11 @@ TestKnobs test_knobs();
 int ensure_csum(Rank& rk, int iters);
 int nb_publish();
 bool pull_requested(const mpx_xfer_opts* o);
+// a Recorder's life (mpx_lat_*, mpx_fan_lat_*; mpx_engine_hostlink.hip: mpx_hostlink_lat_* on a GPU rank)
+int recorder_enable(Rank& me, Recorder& rc, int blocks, int raw_cap, int cap_max, const char* what);
+int recorder_reset(Rank& me, const Recorder& rc);
+int recorder_get(Rank& me, const Recorder& rc, int i, mpx_lat* out);
+int recorder_raw(Rank& me, const Recorder& rc, int i, uint64_t* stamps, int cap, int* n);
 int ensure_peer_tx(mpx_ctx* ctx, Rank& peer, int peer_rank);
 int ensure_peer_tx_locked(mpx_ctx* ctx, Rank& peer, int peer_rank);
 int check_rank_state(mpx_ctx* ctx, int my_rank, const void* tx, const void* rx, const int* peers, int npeers);

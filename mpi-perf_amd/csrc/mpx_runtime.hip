@@ -141,6 +141,7 @@ void free_rank_memory(Rank& rk) {
     if (rk.csum) (void)hipFree(rk.csum);
     if (rk.lat.base) (void)hipFree(rk.lat.base);
     if (rk.fan_lat.base) (void)hipFree(rk.fan_lat.base);
+    if (rk.hostlink_lat.base) (void)hipFree(rk.hostlink_lat.base);
     if (rk.fan_tab) (void)hipFree(rk.fan_tab);
     if (rk.fan_host) (void)hipHostFree(rk.fan_host);
     for (void* q : rk.retired) (void)hipFree(q);
@@ -231,6 +232,9 @@ CopyChoice copy_choice() {
 //                   negative control of tests/test_gpu_ordering.py
 //   no_pull_wait    pull mode: a sending side returns without waiting for the
 //                   peer's loads of its tx (the buffer-reuse negative control)
+//   host_lag=i:us   a host endpoint busy-waits `us` before its first step of
+//                   iteration i of every ping-pong or unidir call (mpx_host_xfer):
+//                   the stalled iteration both ends' host-link recorders must find
 //   fail_launch=r   rank r's kernel-engine calls fail before their kernel is
 //                   enqueued (after take_numbers took their numbers): the
 //                   rollback test of give_back (mpx_engine_kernel.hip)
@@ -264,6 +268,9 @@ TestKnobs test_knobs() {
             if (sscanf(item.c_str() + 7, "%d:%d:%lld", &k.lag_rank, &k.lag_wg, &k.lag_us) != 3) k.lag_rank = -1;
         } else if (item == "no_posted") k.no_posted = true;
         else if (item == "no_pull_wait") k.no_pull_wait = true;
+        else if (!item.compare(0, 9, "host_lag=")) {
+            if (sscanf(item.c_str() + 9, "%d:%lld", &k.host_lag_iter, &k.host_lag_us) != 2) k.host_lag_iter = -1;
+        }
         else if (!item.compare(0, 12, "fail_launch=")) k.fail_launch = atoi(item.c_str() + 12);
         else if (item == "fail_copy") k.fail_copy = true;
         pos = end + 1;
@@ -1417,6 +1424,22 @@ int mpx_fan_lat_raw(mpx_ctx* ctx, int rank, int peer, uint64_t* stamps, int cap,
     if (!me->fan_lat.on) return fail(MPX_ERR_STATE, "rank %d: the link recorder is not enabled", rank);
     return rec_raw(*me, me->fan_lat, peer, stamps, cap, n);
 }
+
+}  // extern "C"
+
+// the Recorder helpers for the host-link recorder's GPU end (mpx_engine_hostlink.hip)
+namespace mpx {
+int recorder_enable(Rank& me, Recorder& rc, int blocks, int raw_cap, int cap_max, const char* what) {
+    return rec_enable(me, rc, blocks, raw_cap, cap_max, what);
+}
+int recorder_reset(Rank& me, const Recorder& rc) { return rec_reset(me, rc); }
+int recorder_get(Rank& me, const Recorder& rc, int i, mpx_lat* out) { return rec_get(me, rc, i, out); }
+int recorder_raw(Rank& me, const Recorder& rc, int i, uint64_t* stamps, int cap, int* n) {
+    return rec_raw(me, rc, i, stamps, cap, n);
+}
+}  // namespace mpx
+
+extern "C" {
 
 int mpx_barrier(mpx_ctx* ctx, int nthreads) {
     if (!ctx || nthreads < 1) return fail(MPX_ERR_INVALID, "bad argument");

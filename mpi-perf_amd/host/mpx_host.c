@@ -31,6 +31,7 @@ void mpxh_defaults(mpxh_options *o)
     o->arm = 1;
     o->lat_cap = -1;
     o->fan_lat_cap = -1;
+    o->hostlink_lat_cap = -1;
 }
 
 int mpxh_engine_from_name(const char *s)
@@ -75,7 +76,8 @@ void mpxh_print_usage(FILE *f)
 		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n\
 		    -H <1|2: each of the -w ranks is a GPU rank paired with a CPU endpoint across the host link;>\n\
 		       <1: the GPU rank sends first (-u 1: device to host), 2: the endpoint does (kernel engine, threads)>\n\
-		    -X <1: with -H, every run is the full-duplex non-blocking loop across the host link (both directions at once)>\n");
+		    -X <1: with -H, every run is the full-duplex non-blocking loop across the host link (both directions at once)>\n\
+		    -T <raw-cap: with -H (not -X 1), record every iteration's latency on both ends of the host link, lat-*.csv>\n");
 }
 
 /* parse_args, mpi_perf.c:273-339 */
@@ -84,7 +86,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:T:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -138,6 +140,13 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
             const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > MPXH_FAN_LAT_RAW_MAX) return MPXH_PARSE_BAD_VALUE;
             o->fan_lat_cap = (int)v;
+            break;
+        }
+        case 'T': {
+            char *end = NULL;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > MPXH_HOSTLINK_LAT_RAW_MAX) return MPXH_PARSE_BAD_HOSTLINK_LAT;
+            o->hostlink_lat_cap = (int)v;
             break;
         }
         default: return MPXH_PARSE_USAGE; /* includes -h and a missing value */
@@ -304,6 +313,16 @@ static int validate_duplex(const mpxh_options *o, FILE *err)
 
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
+    /* -T (the host-link recorder): a -H run of the blocking loops */
+    if (o->hostlink_lat_cap >= 0 && !o->hostlink) {
+        fprintf(err, "invalid -T %d without -H: the host-link recorder traces host-link calls only\n", o->hostlink_lat_cap);
+        return 1;
+    }
+    if (o->hostlink_lat_cap >= 0 && o->duplex) {
+        fprintf(err, "invalid -T %d with -X 1: the full-duplex loop is never traced by the host-link recorder\n",
+                o->hostlink_lat_cap);
+        return 1;
+    }
     if (o->duplex && validate_duplex(o, err)) return 1;
     if (o->hostlink) {
         if (validate_hostlink(o, world, err)) return 1;

@@ -67,6 +67,10 @@ typedef struct mpxh_options {
                                            the host link
                                            (mpx_xfer_hostlink_duplex /
                                            mpx_host_xfer_duplex)              */
+    int hostlink_lat_cap;           /* -T  raw_cap: with -H, record every
+                                           iteration's latency on both ends of
+                                           the host link (mpx_hostlink_lat_*),
+                                           lat-*.csv; -1 (default) = off      */
 } mpxh_options;
 
 /* parse status */
@@ -76,13 +80,14 @@ enum {
     MPXH_PARSE_BAD_VALUE = 2,       /* a value of a new flag is malformed    */
     MPXH_PARSE_CRASH = 3,           /* the reference dereferences a missing
                                        argument (Windows variant)           */
-    MPXH_PARSE_BAD_DUPLEX = 4       /* -X with a value other than 0 or 1     */
+    MPXH_PARSE_BAD_DUPLEX = 4,      /* -X with a value other than 0 or 1     */
+    MPXH_PARSE_BAD_HOSTLINK_LAT = 5 /* -T with a malformed raw_cap           */
 };
 
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:m:P:H:X:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:P:H:X:T:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -110,7 +115,7 @@ int mpxh_fan_peers(int world, int rank, int *peers);
    and a -b too large for world blocks (-m 2: the same, and a -b above
    MPXH_FAN_LL_MAX), and -P without -m 2; -H against -x 1, -a 1, -m, an
    explicit -A 1, -L, -d 1, -e sdma|rccl, processes mode and -w above
-   MPXH_HOSTLINK_MAX_WORLD; then group_size, mpi_perf.c:399-403 (with -H the
+   MPXH_HOSTLINK_MAX_WORLD, and -T without -H or with -X 1; then group_size, mpi_perf.c:399-403 (with -H the
    job is the 2 * world ranks: the GPU ranks and their endpoints).
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides
@@ -147,6 +152,8 @@ void mpxh_format_time(char *buf, size_t cap, int for_kusto);
    (-m 2 -P: one line per link and recorded run, Mode = 10) */
 #define MPXH_FAN_LAT_RAW_MAX (1 << 16) /* MPX_FAN_LAT_RAW_MAX, include/mpx_fan_lat.h */
 #define MPXH_FAN_LAT_MODE 10           /* the LL fan call's protocol number  */
+/* -H -T: one line per end and recorded run, Mode = the call's protocol number (11 LL, 12 bulk) */
+#define MPXH_HOSTLINK_LAT_RAW_MAX (1 << 16) /* MPX_HOSTLINK_LAT_RAW_MAX, include/mpx_hostlink_lat.h */
 #define MPXH_LAT_HEADER                                                                                   \
     "Timestamp,JobId,Rank,PeerRank,Mode,BufferSize,NumOfBuffers,RunId,Count,MinUs,P50Us,P90Us,P99Us,P999Us," \
     "MaxUs,MeanUs,MaxIter\n"

@@ -289,10 +289,10 @@ static void open_logs(int rank, rank_files *f)
         fprintf(f->gpu_fp, "Timestamp,JobId,Rank,Engine,Mode,Device,PeerRank,PeerDevice,BufferSize,NumOfBuffers,"
                            "WallTimems,DeviceTimems,GBps,Protocol,Workgroups,CheckedPayloads,CheckFailures,RunId,RecvDone,"
                            "RecvDigest,Launch,Rccl\n");
-    /* -L, -m 2 -P: the latency side file, opened and rotated with the GPU side file
+    /* -L, -m 2 -P, -H -T: the latency side file, opened and rotated with the GPU side file
        (a name of its own: neither "tcp*" nor "gpu-*.csv" matches it) */
     f->lat_fp = NULL;
-    if (opt.lat_cap >= 0 || opt.fan_lat_cap >= 0) {
+    if (opt.lat_cap >= 0 || opt.fan_lat_cap >= 0 || opt.hostlink_lat_cap >= 0) {
         snprintf(name, sizeof name, "%s/lat-%s-%d-%s.csv", opt.logfolder, opt.uuid, rank, ft);
         f->lat_fp = fopen(name, "w");
         if (f->lat_fp) fputs(MPXH_LAT_HEADER, f->lat_fp);
@@ -321,7 +321,8 @@ static int xfer_mode(void)
 }
 
 /* one lat-*.csv line: a recorded run's distribution (-L: the rank's; -m 2 -P:
-   one link's, mode = MPXH_FAN_LAT_MODE) */
+   one link's, mode = MPXH_FAN_LAT_MODE; -H -T: one end's of the host link, in
+   that end's ticks, mode = the call's protocol number) */
 static void write_lat_line(FILE *fp, const mpx_lat *l, const char *ts, int r, int peer, int mode, int B, long long run_idx)
 {
     char line[1024];
@@ -373,6 +374,11 @@ static void close_logs(rank_files *f)
     if (f->lat_fp) fclose(f->lat_fp);
 }
 
+/* -H -T: every end's distribution and protocol number of its last run */
+_Static_assert(MPXH_HOSTLINK_LAT_RAW_MAX == MPX_HOSTLINK_LAT_RAW_MAX, "-T's limit is the library's");
+static mpx_lat hl_lat_of[MPXH_MAX_RANKS];
+static int hl_proto_of[MPXH_MAX_RANKS];
+
 /* the run loop of one rank, mpi_perf.c:470-569 */
 static void *rank_main(void *arg)
 {
@@ -381,6 +387,9 @@ static void *rank_main(void *arg)
     int prev_group = -1;
     const int lat = opt.lat_cap >= 0 && !opt.use_dotnet;
     if (lat) MPX_CHECK(mpx_lat_enable(ctx, r, opt.lat_cap));
+    /* -T: both ends of every host link record (validated: -H, not -X 1) */
+    const int hl_lat = opt.hostlink_lat_cap >= 0;
+    if (hl_lat) MPX_CHECK(mpx_hostlink_lat_enable(ctx, r, opt.hostlink_lat_cap));
     for (int si = 0; si < nsizes; ++si) {
         const int B = sizes[si];
         for (long long run_idx = 0; opt.num_runs == -1 || run_idx < opt.num_runs; run_idx++) {
@@ -425,6 +434,7 @@ static void *rank_main(void *arg)
             /* -L: every run's distribution is its own (before the arm: an
                armed rank's recorder cannot be touched) */
             if (lat) MPX_CHECK(mpx_lat_reset(ctx, r));
+            if (hl_lat) MPX_CHECK(mpx_hostlink_lat_reset(ctx, r));
             /* -A 1: the run's kernel is launched now and started by the
                mpx_xfer_ex after the barrier (MPI_Start of a persistent
                request), so the launch is not inside the timed loop */
@@ -449,6 +459,13 @@ static void *rank_main(void *arg)
                 MPX_CHECK(mpx_xfer_ex(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
             }
             const double my_time = wtime() - t_start; /* mpi_perf.c:532-533 */
+            /* -T: this end's distribution and protocol, for the rank that
+               holds the link's log files (read between this end's calls;
+               that rank looks behind the run's barrier) */
+            if (hl_lat) {
+                MPX_CHECK(mpx_hostlink_lat_get(ctx, r, peer, &hl_lat_of[r]));
+                hl_proto_of[r] = tm.protocol;
+            }
 
             if (report_bandwidth && group == 0) {
                 char line[256];
@@ -487,6 +504,15 @@ static void *rank_main(void *arg)
             }
 
             end_run(r, run_idx, t_start, my_time);
+            /* -T: a line per end of the link, each in its own clock's ticks
+               (the peer cannot store its next run's before this rank joins
+               that run's barrier) */
+            if (hl_lat && run_idx > 0 && group == 1 && files.lat_fp) {
+                char ts[MPXH_MAX_HOST] = {0};
+                mpxh_format_time(ts, sizeof ts, 1);
+                write_lat_line(files.lat_fp, &hl_lat_of[r], ts, r, peer, hl_proto_of[r], B, run_idx);
+                write_lat_line(files.lat_fp, &hl_lat_of[peer], ts, peer, r, hl_proto_of[peer], B, run_idx);
+            }
         }
     }
     close_logs(&files);
@@ -733,6 +759,13 @@ int main(int argc, char **argv)
     if (pst == MPXH_PARSE_BAD_DUPLEX) {
         if (is_root()) {
             fprintf(stderr, "bad value for -X (0 or 1)\n");
+            mpxh_print_usage(stderr);
+        }
+        mpx_abort();
+    }
+    if (pst == MPXH_PARSE_BAD_HOSTLINK_LAT) {
+        if (is_root()) {
+            fprintf(stderr, "bad value for -T (a raw-cap of 0 to %d)\n", MPXH_HOSTLINK_LAT_RAW_MAX);
             mpxh_print_usage(stderr);
         }
         mpx_abort();

@@ -134,6 +134,7 @@ class Phases(C.Structure):
 LAT_BUCKETS = 464
 LAT_RAW_MAX = 1 << 22
 FAN_LAT_RAW_MAX = 1 << 16   # MPX_FAN_LAT_RAW_MAX: the link recorder's (fan_lat_enable)
+HOSTLINK_LAT_RAW_MAX = 1 << 16   # MPX_HOSTLINK_LAT_RAW_MAX: the host-link recorder's (hostlink_lat_enable)
 
 
 class Lat(C.Structure):
@@ -235,6 +236,11 @@ _SIGS = {
     "mpx_fan_lat_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "mpx_fan_lat_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Lat)]),
     "mpx_fan_lat_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
+    "mpx_hostlink_lat_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mpx_hostlink_lat_disable": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_hostlink_lat_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "mpx_hostlink_lat_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Lat)]),
+    "mpx_hostlink_lat_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]),
     "mpx_host_attach": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t]),
     "mpx_host_buffers": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mpx_xfer_hostlink": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -369,6 +375,7 @@ class Context:
         self.engine = engine
         self._lat_cap = {}   # rank -> raw_cap of its latency recorder (lat_enable)
         self._fan_lat_cap = {}   # rank -> raw_cap of its link recorder (fan_lat_enable)
+        self._hostlink_lat_cap = {}   # rank -> raw_cap of its host-link recorder (hostlink_lat_enable)
         self._host_len = {}      # host endpoint -> its attached length (host_attach)
 
     def close(self) -> None:
@@ -648,6 +655,30 @@ class Context:
         """mpx_fan_lat_raw: link (rank, peer)'s stamps t[0 .. min(iters, raw_cap)]
         of the last traced call that listed peer (cap: at most that many)"""
         return self._lat_stamps("mpx_fan_lat_raw", self._fan_lat_cap, cap, rank, peer)
+
+    # host-link recorder (include/mpx_hostlink_lat.h): rank is a GPU rank or a host endpoint
+    def hostlink_lat_enable(self, rank: int, raw_cap: int = 0) -> None:
+        """mpx_hostlink_lat_enable: trace every host-link call of rank (a GPU
+        rank: xfer_hostlink; an endpoint: host_xfer) from now on, per peer,
+        keeping the first raw_cap iterations' stamps of each call; resets"""
+        check(self.L.mpx_hostlink_lat_enable(self.h, rank, raw_cap), "mpx_hostlink_lat_enable")
+        self._hostlink_lat_cap[rank] = raw_cap
+
+    def hostlink_lat_disable(self, rank: int) -> None:
+        check(self.L.mpx_hostlink_lat_disable(self.h, rank), "mpx_hostlink_lat_disable")
+
+    def hostlink_lat_reset(self, rank: int) -> None:
+        check(self.L.mpx_hostlink_lat_reset(self.h, rank), "mpx_hostlink_lat_reset")
+
+    def hostlink_lat_get(self, rank: int, peer: int) -> dict:
+        """mpx_hostlink_lat_get: link (rank, peer)'s distribution since enable /
+        reset (the dict of lat_get; tick_s is 1e-8 on a GPU rank, 1e-9 on an endpoint)"""
+        return self._lat_dict("mpx_hostlink_lat_get", rank, peer)
+
+    def hostlink_lat_raw(self, rank: int, peer: int, cap: int | None = None) -> list[int]:
+        """mpx_hostlink_lat_raw: link (rank, peer)'s stamps t[0 .. min(iters, raw_cap)]
+        of the last traced call with that peer (cap: at most that many)"""
+        return self._lat_stamps("mpx_hostlink_lat_raw", self._hostlink_lat_cap, cap, rank, peer)
 
     def rccl_init_all(self) -> None:
         check(self.L.mpx_rccl_init_all(self.h), "mpx_rccl_init_all")

@@ -48,6 +48,26 @@ process, so the figures stand beside each other's:
     numa              as above.
 
     python tools/hostlink_probe.py --duplex
+
+--lat measures the host-link recorder (include/mpx_hostlink_lat.h) and APPENDS
+its lines to profiles/hostlink_lat.jsonl (--out), all from one process:
+
+    lat_off           tracing off: the 8 B ping-pong half round trip, both
+                      orientations (5 calls of 2000 iterations), and the 4 MiB
+                      unidir rate, both directions (5 calls of 50), with the
+                      library's file name (MPX_LIB: the same figures from
+                      another build with the recorder's symbols).  --lat-off-only
+                      stops here.
+    lat_observer      traced - untraced per iteration at 8 B ping-pong and
+                      4 MiB unidir, with the GPU end traced only, the endpoint
+                      only, and both: 5 interleaved rounds, medians.
+    lat_distribution  8 B ping-pong, 100 000 iterations x 5 calls, and 4 MiB
+                      unidir x 500 x 5: both ends' p50 / p99 / p99.9 / max and
+                      the iteration of the maximum per call, and whether the
+                      two ends name the same iteration as the slowest.
+    numa              as above.
+
+    python tools/hostlink_probe.py --lat
 """
 import argparse
 import ctypes as C
@@ -63,9 +83,14 @@ ap.add_argument("--calls", type=int, default=5)
 ap.add_argument("--bw-bytes", type=int, default=4 << 20)
 ap.add_argument("--bw-iters", type=int, default=50)
 ap.add_argument("--duplex", action="store_true", help="measure the full-duplex loop; appends to --out")
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                              "hostlink_duplex.jsonl"))
+ap.add_argument("--lat", action="store_true", help="measure the host-link recorder; appends to --out")
+ap.add_argument("--lat-off-only", action="store_true", help="with --lat: the tracing-off figures only")
+ap.add_argument("--lat-iters", type=int, default=100000)
+ap.add_argument("--out", default=None, help="default: profiles/hostlink_duplex.jsonl, with --lat profiles/hostlink_lat.jsonl")
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                            "hostlink_lat.jsonl" if args.lat else "hostlink_duplex.jsonl")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-perf_amd"))
 import mpx  # noqa: E402
 
@@ -257,9 +282,101 @@ def duplex_probe():
         f.write("\n".join(lines) + "\n")
 
 
+# ---- the host-link recorder (--lat) ------------------------------------------------
+def lat_probe():
+    B, IT = args.bw_bytes, args.bw_iters
+    lines = []
+    clock = "kernel (s_memrealtime), posted wait excluded"
+
+    def emit(**kw):
+        lines.append(json.dumps(dict(kind=KIND, **kw)))
+        print(lines[-1], flush=True)
+
+    # tracing off (any build of the library)
+    for gpu_group in (1, 0):
+        call(mpx.MODE_PINGPONG, gpu_group, 8, 2000)
+        v = [call(mpx.MODE_PINGPONG, gpu_group, 8, 2000)[0] / 2000 / 2 for _ in range(args.calls)]
+        emit(item="lat_off", what="8 B ping-pong half round trip", gpu_group=gpu_group, calls=args.calls, iters=2000,
+             half_rtt_us=spread(v, 1e6), per_call_us=[round(x * 1e6, 3) for x in v], lib=os.path.basename(mpx.LIB_PATH), clock=clock)
+    for gpu_group, direction in ((1, "device_to_host"), (0, "host_to_device")):
+        call(mpx.MODE_UNIDIR, gpu_group, B, 5)
+        v = [B * IT / call(mpx.MODE_UNIDIR, gpu_group, B, IT)[0] / 1e9 for _ in range(args.calls)]
+        emit(item="lat_off", what="unidir rate", direction=direction, bytes=B, calls=args.calls, iters=IT,
+             GBps=spread(v, 1, 2), per_call_GBps=[round(x, 2) for x in v], lib=os.path.basename(mpx.LIB_PATH), clock=clock)
+    if args.lat_off_only:
+        return lines
+
+    # the observer's cost: traced - untraced per iteration, interleaved rounds
+    arms = (("untraced", ()), ("gpu_traced", (G,)), ("endpoint_traced", (E,)), ("both_traced", (G, E)))
+    for what, mode, gpu_group, n, iters in (("8 B ping-pong", mpx.MODE_PINGPONG, 1, 8, 2000),
+                                            ("8 B ping-pong", mpx.MODE_PINGPONG, 0, 8, 2000),
+                                            ("4 MiB unidir", mpx.MODE_UNIDIR, 1, B, IT),
+                                            ("4 MiB unidir", mpx.MODE_UNIDIR, 0, B, IT)):
+        per = {name: [] for name, _ in arms}
+        call(mode, gpu_group, n, iters)
+        for _ in range(5):
+            for name, on in arms:
+                for r in on:
+                    c.hostlink_lat_enable(r, 0)
+                per[name].append(call(mode, gpu_group, n, iters)[0] / iters)
+                for r in on:
+                    c.hostlink_lat_disable(r)
+        med = {k: statistics.median(v) for k, v in per.items()}
+        emit(item="lat_observer", what=what, gpu_group=gpu_group, bytes=n, iters=iters, rounds=5,
+             per_iteration_us={k: spread(v, 1e6) for k, v in per.items()},
+             traced_minus_untraced_us={k: round((med[k] - med["untraced"]) * 1e6, 3) for k in med if k != "untraced"},
+             clock=clock)
+
+    # the distribution itself, on both ends
+    def us(lat, ticks):
+        return round(ticks * lat["tick_s"] * 1e6, 3)
+
+    for what, mode, gpu_group, n, iters in (("8 B ping-pong", mpx.MODE_PINGPONG, 1, 8, args.lat_iters),
+                                            ("4 MiB unidir, device to host", mpx.MODE_UNIDIR, 1, B, 500)):
+        for r in (G, E):
+            c.hostlink_lat_enable(r, 0)
+        call(mode, gpu_group, n, min(iters, 2000))
+        per_call, agree = [], 0
+        for _ in range(5):
+            for r in (G, E):
+                c.hostlink_lat_reset(r)
+            call(mode, gpu_group, n, iters)
+            row = {}
+            for name, r, peer in (("gpu", G, E), ("endpoint", E, G)):
+                lat = c.hostlink_lat_get(r, peer)
+                row[name] = dict(count=lat["count"], min_us=us(lat, lat["min_ticks"]),
+                                 p50_us=us(lat, mpx.lat_quantile(lat, 0.5)), p99_us=us(lat, mpx.lat_quantile(lat, 0.99)),
+                                 p999_us=us(lat, mpx.lat_quantile(lat, 0.999)), max_us=us(lat, lat["max_ticks"]),
+                                 mean_us=us(lat, lat["sum_ticks"] / max(lat["count"], 1)), max_iter=lat["max_iter"])
+            agree += row["gpu"]["max_iter"] == row["endpoint"]["max_iter"]
+            per_call.append(row)
+        for r in (G, E):
+            c.hostlink_lat_disable(r)
+        emit(item="lat_distribution", what=what, gpu_group=gpu_group, bytes=n, iters=iters, calls=5,
+             unit="one iteration: a round trip (ping-pong) or one payload and its ack (unidir)", per_call=per_call,
+             calls_where_both_ends_name_the_same_slowest_iteration=agree,
+             clocks="gpu: s_memrealtime, 10 ns ticks; endpoint: CLOCK_MONOTONIC, ns")
+    try:
+        gpu_node = int(open(f"/sys/bus/pci/devices/{mpx.bus_id(0).lower()}/numa_node").read())
+    except OSError:
+        gpu_node = None
+    emit(item="numa", binding="not controlled: no thread or allocation was bound to a node", gpu_numa_node=gpu_node,
+         endpoint_tx_node=node_of_page(C.addressof(htx)), endpoint_rx_node=node_of_page(C.addressof(hrx)),
+         gpu_side_thread=dict(cpu=cpu_of.get(G), node=node_of_cpu(cpu_of.get(G, -1))),
+         endpoint_thread=dict(cpu=cpu_of.get(E), node=node_of_cpu(cpu_of.get(E, -1))))
+    return lines
+
+
 if args.duplex:
     duplex_probe()
     c.close()
+    sys.exit(0)
+if args.lat:
+    out_lines = lat_probe()
+    c.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(out_lines) + "\n")
     sys.exit(0)
 
 # ---- latency ------------------------------------------------------------------
