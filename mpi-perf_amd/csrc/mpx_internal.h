@@ -385,7 +385,81 @@ hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s);
 // loop on a split grid of 2 * a.nwg workgroups; the same boxes and slots
 constexpr int kDuplexMaxWG = kMaxPushWG / 2;   // per direction
 hipError_t launch_hostlink_duplex(const XferArgs& a, hipStream_t s);
-hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out);
+// k_copy_win's resident window (DESIGN.md "k_copy tuning: the resident window").
+// A copy is a row of 4 KiB blocks, one per workgroup.  Block b of src is
+// loaded with the default cache policy, so that it stays in the 256 MiB
+// Infinity Cache for the next copy of the same buffer, when
+//     (b / unit) % period < window        (unit in blocks, period and window in units)
+// and nontemporal, as every store, otherwise.  unit and period are powers of
+// two: the kernel's test is a shift, a mask and a compare.  on = false is
+// k_copy, the kernel without the choice.
+struct CopyWindow {
+    bool on = false;
+    unsigned unit = 1, period = 1, window = 0;
+};
+constexpr size_t kCopyBlockBytes = 4096;
+// The rule: a function of the copy's size alone, so repeated copies of the
+// same pointers keep the same lines and no call needs to know of another.
+// Constants from profiles/copy_window_lab.jsonl (1 GiB, form win_PL_*):
+// stripes of 1 MiB units, 32 to a period, and as many units kept per period
+// as hold kCopyWindowCap bytes resident over the whole copy.  Off below
+// kCopyWindowMin (not landed below it: DESIGN.md) and where even one unit per
+// period would pass the cap.
+constexpr size_t kCopyWindowMin = (size_t)512 << 20;
+constexpr size_t kCopyWindowCap = (size_t)192 << 20;
+constexpr unsigned kCopyWindowUnit = 256, kCopyWindowPeriod = 32;
+inline CopyWindow copy_window_rule(size_t n) {
+    CopyWindow w;
+    if (n < kCopyWindowMin) return w;
+    const size_t period_bytes = (size_t)kCopyWindowUnit * kCopyWindowPeriod * kCopyBlockBytes;
+    const size_t periods = (n + period_bytes - 1) / period_bytes;          // a partial last period counts as one
+    const size_t units = kCopyWindowCap / ((size_t)kCopyWindowUnit * kCopyBlockBytes) / periods;
+    if (!units) return w;
+    w.on = true;
+    w.unit = kCopyWindowUnit;
+    w.period = kCopyWindowPeriod;
+    w.window = units < kCopyWindowPeriod ? (unsigned)units : kCopyWindowPeriod;
+    return w;
+}
+// MPX_COPY_WINDOW="period:window[:unit]" (read per call, like MPX_COPY; the
+// tests and the A/B drive the kernel with it).  unit is in bytes (default
+// 4096).  period and window are COUNTS OF UNITS written x 4096, as in the
+// kernel's test above: the period in bytes is period / 4096 x unit, and the
+// rule's choice at 1 GiB reads "131072:24576:1048576".  Every value is a
+// multiple of 4096, unit / 4096 and period / 4096 are powers of two (the
+// kernel shifts and masks), window <= period.  "0" is off: the kernel
+// without the choice.  Returns false, with *w off, for anything else; *w is
+// the rule's choice when v is null or empty.
+inline bool copy_window_parse(const char* v, size_t n, CopyWindow* w) {
+    *w = copy_window_rule(n);
+    if (!v || !*v) return true;
+    *w = CopyWindow();
+    unsigned long long f[3] = {0, 0, kCopyBlockBytes};
+    int k = 0;
+    for (const char* p = v;; ++k) {
+        if (k == 3 || *p < '0' || *p > '9') return false;
+        unsigned long long x = 0;
+        for (; *p >= '0' && *p <= '9'; ++p) {
+            if (x > (1ull << 40)) return false;
+            x = x * 10 + (unsigned long long)(*p - '0');
+        }
+        f[k] = x;
+        if (!*p) break;
+        if (*p++ != ':') return false;
+    }
+    if (k == 0) return f[0] == 0;
+    const unsigned long long B = kCopyBlockBytes;
+    if (f[0] % B || f[1] % B || f[2] % B || !f[0] || !f[2] || f[1] > f[0]) return false;
+    const unsigned long long period = f[0] / B, unit = f[2] / B;
+    if ((period & (period - 1)) || (unit & (unit - 1)) || period > (1u << 30) || unit > (1u << 30)) return false;
+    w->on = true;
+    w->unit = (unsigned)unit;
+    w->period = (unsigned)period;
+    w->window = (unsigned)(f[1] / B);
+    return true;
+}
+hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out,
+                       const CopyWindow& win = CopyWindow());
 // all `iters` copies in one launch with a grid barrier between steps; *bar
 // must be 0 at launch
 constexpr int kCopyStepsMaxGrid = 1024;   // 4 workgroups per CU: always co-resident

@@ -2,6 +2,7 @@
 //
 // Kernels
 //   k_copy      local HBM copy, one 16-B unit per lane, one step per block (config 2)
+//   k_copy_win  the same with part of src kept in the Infinity Cache (from 512 MiB)
 //   k_xfer      the reference's three transfer loops as ONE persistent launch
 //               per rank: pushes go straight into the peer's HBM over xGMI,
 //               receives are device-side polls of the rank's mailbox
@@ -119,6 +120,36 @@ __global__ __launch_bounds__(kBlock) void k_copy(const v4u* __restrict__ src, v4
     }
     for (; i < end; i += stride) st16<STNT>(dst + i, ld16<LDNT>(src + i));
     if (blockIdx.x == 0 && threadIdx.x < tail) {
+        const unsigned char* s8 = reinterpret_cast<const unsigned char*>(src + n16);
+        unsigned char* d8 = reinterpret_cast<unsigned char*>(dst + n16);
+        d8[threadIdx.x] = s8[threadIdx.x];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_copy_win: launch_copy's form of k_copy (one 16-B unit per lane, one step
+// per block, nontemporal stores) with the load's cache policy chosen per
+// workgroup (CopyWindow, mpx_internal.h).  Workgroup b copies 4 KiB block b;
+// a kept block, ((b >> shift) & mask) < units, loads with the default policy
+// so that it stays in the Infinity Cache for the next copy of src.  The
+// branch is uniform.  The kept load is a buffer load, the streamed one a
+// nontemporal pointer load: two loads of one pointer that differ only in the
+// hint are merged into one plain load under __restrict__, which drops the hint.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_copy_win(const v4u* __restrict__ src, v4u* __restrict__ dst, size_t n16,
+                                                    unsigned tail, unsigned shift, unsigned mask, unsigned units) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (((blockIdx.x >> shift) & mask) < units) {
+        // the descriptor covers this block's whole units only: a lane past n16 loads nothing
+        const size_t left = n16 - (size_t)blockIdx.x * kBlock;   // > 0: the grid is ceil(n16 / kBlock)
+        const unsigned bytes = left < (size_t)kBlock ? (unsigned)left * 16 : kBlock * 16;
+        const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rsrc(src + (size_t)blockIdx.x * kBlock, bytes),
+                                                            threadIdx.x * 16, 0, 0);
+        if (i < n16) st16<true>(dst + i, r);
+    } else if (i < n16) {
+        st16<true>(dst + i, ld16<true>(src + i));
+    }
+    if (blockIdx.x == 0 && threadIdx.x < tail) {   // the tail bytes, as k_copy
         const unsigned char* s8 = reinterpret_cast<const unsigned char*>(src + n16);
         unsigned char* d8 = reinterpret_cast<unsigned char*>(dst + n16);
         d8[threadIdx.x] = s8[threadIdx.x];
@@ -2361,7 +2392,9 @@ hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s) {
 // for hipMemcpyAsync device-to-device.  The 39 other instantiations of round
 // 1-3's variant knob (unroll x load/store policy x layout) are gone; their
 // evidence stays in profiles/copy_sweep_r01.jsonl and r01_copy_policy_*.
-hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out) {
+// win.on: k_copy_win, the same form with a striped part of src loaded with
+// the default policy (the rule and its evidence at copy_window_rule).
+hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int* grid_out, const CopyWindow& win) {
     const size_t n16 = n / 16;
     const unsigned tail = (unsigned)(n & 15);
     size_t grid = (n16 + (size_t)kBlock - 1) / (size_t)kBlock;
@@ -2369,6 +2402,13 @@ hipError_t launch_copy(void* dst, const void* src, size_t n, hipStream_t s, int*
     if (grid > ((size_t)1 << 31) - 1) return hipErrorInvalidValue;
     if (grid_out) *grid_out = (int)grid;
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
+    if (win.on) {
+        // n16 == 0 (n < 16): one workgroup, nothing kept, only the tail bytes
+        hipLaunchKernelGGL(k_copy_win, dim3((unsigned)grid), dim3(kBlock), 0, s, reinterpret_cast<const v4u*>(src),
+                           reinterpret_cast<v4u*>(dst), n16, tail, (unsigned)__builtin_ctz(win.unit), win.period - 1,
+                           n16 ? win.window : 0u);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((k_copy<1, true, true, false>), dim3((unsigned)grid), dim3(kBlock), 0, s,
                        reinterpret_cast<const v4u*>(src), reinterpret_cast<v4u*>(dst), n16, tail);
     return hipGetLastError();

@@ -190,6 +190,8 @@ int ensure_ring(Rank& rk) {
 //   "launch"                      a k_copy launch per copy, any size
 //   "steps[:cap:xcd:drain:upl:threads:one_xcd]"   k_copy_steps at any size
 //   "pipe[:upl[:hier]]"           k_copy_pipe at any size it can hold
+// MPX_COPY_WINDOW (read per call too): k_copy_win's resident window, see
+// copy_window_parse (mpx_internal.h).
 // Round 3's six copy knobs (MPX_COPY_VARIANT, _STEPS, _STEPS_MAX,
 // _PIPE_MIN, _PIPE_MAX, _PIPE_UPL, _PIPE_HIER) are this one.
 enum CopyForm { kCopyAuto = 0, kCopyLaunch, kCopySteps, kCopyPipe };
@@ -771,6 +773,12 @@ int mpx_copy(mpx_ctx* ctx, int dev, void* dst, const void* src, size_t n, int it
     // k_copy launch per copy above (profiles/r03_copy_pipe_ab.jsonl, DESIGN.md
     // §5) — or the form MPX_COPY forces (copy_choice)
     const CopyChoice cc = copy_choice();
+    // a launch per copy: which blocks of src stay in the Infinity Cache for the
+    // next copy (copy_window_rule, or the window MPX_COPY_WINDOW forces)
+    CopyWindow win;
+    if (!copy_window_parse(getenv("MPX_COPY_WINDOW"), n, &win))
+        return fail(MPX_ERR_INVALID, "MPX_COPY_WINDOW is not \"period:window[:unit]\" (multiples of 4096, "
+                                     "period / 4096 and unit / 4096 powers of two, window <= period) or \"0\"");
     const bool multi = n && iters > 1;
     bool pipe = multi && (cc.form == kCopyPipe ||
                           (cc.form == kCopyAuto && n > kCopyPipeDefaultMin && n <= kCopyPipeDefaultMax));
@@ -797,7 +805,7 @@ int mpx_copy(mpx_ctx* ctx, int dev, void* dst, const void* src, size_t n, int it
         } else if (one)
             HIPCK(launch_copy_steps(dst, src, n, iters, bar, s, &grid, cc.shaped ? cc.shape : nullptr));
         else
-            for (int i = 0; i < iters && n; ++i) HIPCK(launch_copy(dst, src, n, s, &grid));
+            for (int i = 0; i < iters && n; ++i) HIPCK(launch_copy(dst, src, n, s, &grid, win));
         HIPCK(hipEventRecord(e1, s));
         HIPCK(hipEventSynchronize(e1));
         HIPCK(hipEventElapsedTime(&ms, e0, e1));

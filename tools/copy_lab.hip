@@ -3,6 +3,8 @@
 // Times every variant over a 1 GiB copy with HIP events (avg of 20 launches,
 // best of 5 reps) and checks the output.  One JSON line per variant.
 //   hipcc --offload-arch=gfx950 -O3 -o tools/copy_lab tools/copy_lab.hip
+//   tools/copy_lab <bytes> [filter [dst_off src_off]]    the variant table
+//   tools/copy_lab <bytes> win|win2 [filter [filter]]    the window lab (below)
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -164,8 +166,197 @@ template <int T, int U> void runD(const void* s, void* d, size_t n, int g, int, 
     hipLaunchKernelGGL((kD<T, U>), dim3(g), dim3(T), 0, st, (const v4u*)s, (v4u*)d, n / 16);
 }
 
+// ---------------------------------------------------------------------------
+// Window lab (`copy_lab <bytes> win [filter]`): can a striped subset of a
+// repeatedly copied buffer stay in the 256 MiB Infinity Cache while the rest
+// streams past it?  The shipped shape (one 16-B unit per lane, one step per
+// workgroup) with the cache policy picked per workgroup: 4 KiB block b is
+// "kept" when (b / unit) % period < window (unit in blocks, period and window
+// in units; unit and period are powers of two, so the test is a shift, a mask
+// and a compare on the scalar unit).  Kept blocks use aux LA on the load (LW)
+// and / or default-policy stores (SW); every other access is nontemporal.
+// The branch is uniform and the two buffer loads carry different constant
+// aux, so they cannot be merged.  Results: profiles/copy_window_lab.jsonl.
+struct Win { unsigned unit_shift, period_mask, window; };
+template <int LA, bool LW, bool SW>
+__global__ __launch_bounds__(256) void kWin(const unsigned char* s, unsigned char* d, size_t n, Win w) {
+    const size_t lo = (size_t)blockIdx.x * 4096;
+    const unsigned bytes = n - lo < 4096 ? (unsigned)(n - lo) & ~15u : 4096u;   // the buffer bounds the last block
+    const __amdgpu_buffer_rsrc_t rs = rsrc(s + lo, bytes), rd = rsrc(d + lo, bytes);
+    const unsigned o = threadIdx.x * 16;
+    if (((blockIdx.x >> w.unit_shift) & w.period_mask) < w.window) {
+        const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, LW ? LA : 2);
+        __builtin_amdgcn_raw_buffer_store_b128(r, rd, o, 0, SW ? 0 : 2);
+    } else {
+        const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, 2);
+        __builtin_amdgcn_raw_buffer_store_b128(r, rd, o, 0, 2);
+    }
+}
+// The same with the shipped instructions on every block that is not kept: a
+// nontemporal pointer load and store, as kE<256, 1>.  Only a kept block goes
+// through a buffer descriptor (default policy).  A pointer load and a buffer
+// load cannot be merged either, and the streamed blocks pay nothing for the
+// descriptor (`copy_lab <bytes> win2`).
+template <bool LW, bool SW>
+__global__ __launch_bounds__(256) void kWinP(const unsigned char* s, unsigned char* d, size_t n, Win w) {
+    const size_t n16 = n / 16, i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const v4u* sp = (const v4u*)s;
+    v4u* dp = (v4u*)d;
+    if (((blockIdx.x >> w.unit_shift) & w.period_mask) < w.window) {
+        const size_t lo = (size_t)blockIdx.x * 4096;
+        const unsigned bytes = n - lo < 4096 ? (unsigned)(n - lo) & ~15u : 4096u;
+        const unsigned o = threadIdx.x * 16;
+        v4u r;
+        if (LW) r = __builtin_amdgcn_raw_buffer_load_b128(rsrc(s + lo, bytes), o, 0, 0);
+        else if (i < n16) r = __builtin_nontemporal_load(sp + i);
+        if (SW) __builtin_amdgcn_raw_buffer_store_b128(r, rsrc(d + lo, bytes), o, 0, 0);
+        else if (i < n16) __builtin_nontemporal_store(r, dp + i);
+    } else if (i < n16) {
+        __builtin_nontemporal_store(__builtin_nontemporal_load(sp + i), dp + i);
+    }
+}
+typedef void (*WinKernel)(const unsigned char*, unsigned char*, size_t, Win);
+struct WinVar { char name[48]; WinKernel k; Win w; };   // k == nullptr: the shipped form, E_t256_u1
+static void win_run(const WinVar& v, const void* s, void* d, size_t n, hipStream_t st) {
+    if (!v.k) return runE<256, 1>(s, d, n, 0, 0, st);
+    hipLaunchKernelGGL(v.k, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, st, (const unsigned char*)s,
+                       (unsigned char*)d, n, v.w);
+}
+struct WinTimes { double one, many, fresh; };   // us per copy
+// One repetition of one form: a single timed copy after a priming one, 20
+// copies behind one start, and the no-reuse control: `pairs` buffer pairs in
+// rotation (3 at 1 GiB), so a line returns only after 2 * pairs * n bytes.
+static WinTimes win_measure(const WinVar& v, char* const* s, char* const* d, int pairs, size_t n, hipStream_t st,
+                            hipEvent_t e0, hipEvent_t e1) {
+    WinTimes t;
+    float ms;
+    win_run(v, s[0], d[0], n, st);
+    CK(hipEventRecord(e0, st));
+    win_run(v, s[0], d[0], n, st);
+    CK(hipEventRecord(e1, st));
+    CK(hipEventSynchronize(e1));
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    t.one = ms * 1e3;
+    CK(hipEventRecord(e0, st));
+    for (int l = 0; l < 20; ++l) win_run(v, s[0], d[0], n, st);
+    CK(hipEventRecord(e1, st));
+    CK(hipEventSynchronize(e1));
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    t.many = ms * 1e3 / 20;
+    for (int p = 0; p < pairs; ++p) win_run(v, s[p], d[p], n, st);
+    CK(hipEventRecord(e0, st));
+    for (int l = 0; l < 2 * pairs; ++l) win_run(v, s[l % pairs], d[l % pairs], n, st);
+    CK(hipEventRecord(e1, st));
+    CK(hipEventSynchronize(e1));
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    t.fresh = ms * 1e3 / (2 * pairs);
+    CK(hipGetLastError());
+    return t;
+}
+static void win_stats(const double* x, int k, double* lo, double* med, double* hi) {
+    std::vector<double> v(x, x + k);
+    for (int i = 0; i < k; ++i) for (int j = i + 1; j < k; ++j) if (v[j] < v[i]) { double t = v[i]; v[i] = v[j]; v[j] = t; }
+    *lo = v[0], *med = v[k / 2], *hi = v[k - 1];
+}
+static int win_lab(size_t n, const char* only, const char* also, bool second) {
+    const int kReps = 5;
+    const size_t MiB = 1ull << 20;
+    const int pairs = (int)((3ull << 30) / n) < 3 ? 3 : (int)((3ull << 30) / n);
+    std::vector<char*> s(pairs), d(pairs);
+    unsigned* bad;
+    hipStream_t st;
+    CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (int p = 0; p < pairs; ++p) {
+        CK(hipMalloc(&s[p], n));
+        CK(hipMalloc(&d[p], n));
+        hipLaunchKernelGGL(kfill, dim3(4096), dim3(256), 0, st, (unsigned*)s[p], n / 4);
+    }
+    CK(hipMalloc(&bad, 4));
+    CK(hipStreamSynchronize(st));
+    // W MiB resident out of n as window / 32 units of every period (both: the
+    // same units of src and dst, W / 2 each, so 64 units to a period); a form
+    // whose period does not fit n is left out.  aux: sc0 = 1, nt = 2, sc1 = 16
+    struct Form { const char* tag; WinKernel k; bool both; };
+    struct Unit { const char* name; size_t bytes; };
+    const std::vector<Form> forms =
+        !second ? std::vector<Form>{{"L0", kWin<0, true, false>, false}, {"L1", kWin<1, true, false>, false},
+                                    {"L16", kWin<16, true, false>, false}, {"L17", kWin<17, true, false>, false},
+                                    {"S", kWin<0, false, true>, false},      // the mirror image: a window of dst
+                                    {"LS", kWin<0, true, true>, true}}
+                : std::vector<Form>{{"PL", kWinP<true, false>, false}, {"PS", kWinP<false, true>, false},
+                                    {"PLS", kWinP<true, true>, true}};
+    // win2: finer units, and W up to past the cache's size
+    const std::vector<Unit> units = !second ? std::vector<Unit>{{"64K", 64 << 10}, {"1M", 1 << 20}, {"16M", 16 << 20}}
+                                            : std::vector<Unit>{{"64K", 64 << 10}, {"256K", 256 << 10}, {"1M", 1 << 20}, {"4M", 4 << 20}};
+    const std::vector<size_t> Ws = !second ? std::vector<size_t>{64, 128, 160, 192, 224}
+                                           : std::vector<size_t>{96, 128, 160, 192, 224, 256, 320};
+    const WinVar base = {"E_t256_u1", nullptr, {0, 0, 0}};
+    // first the form itself with no block kept
+    std::vector<WinVar> vs = {second ? WinVar{"win_Pallnt", kWinP<true, false>, {0, 0, 0}}
+                                     : WinVar{"win_allnt", kWin<0, true, false>, {0, 0, 0}}};
+    for (const Form& f : forms)
+        for (const Unit& u : units) {
+            size_t lastW = 0;
+            for (size_t W : Ws) {
+                if (W * MiB > n) W = n / MiB;
+                const unsigned period = f.both ? 64 : 32;
+                if (W == lastW || u.bytes * period > n) continue;
+                lastW = W;
+                WinVar v;
+                snprintf(v.name, sizeof v.name, "win_%s_W%zu_u%s", f.tag, W, u.name);
+                v.k = f.k;
+                v.w = {(unsigned)__builtin_ctzll(u.bytes / 4096), period - 1, (unsigned)(W * MiB * 32 / n)};
+                vs.push_back(v);
+            }
+        }
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    for (int w = 0; w < 3; ++w) win_run(base, s[0], d[0], n, st);   // clocks up
+    for (const WinVar& v : vs) {
+        if ((only && !strstr(v.name, only)) || (also && !strstr(v.name, also))) continue;
+        CK(hipMemsetAsync(d[0], 0, n, st));
+        win_run(v, s[0], d[0], n, st);
+        CK(hipGetLastError());
+        CK(hipMemsetAsync(bad, 0, 4, st));
+        hipLaunchKernelGGL(kcmp, dim3(4096), dim3(256), 0, st, (const unsigned*)s[0], (const unsigned*)d[0], n / 4, bad);
+        unsigned nb = 0;
+        CK(hipMemcpyAsync(&nb, bad, 4, hipMemcpyDeviceToHost, st));
+        CK(hipStreamSynchronize(st));
+        double t[2][3][kReps];   // [base, variant][one, many, fresh][rep]
+        for (int rep = 0; rep < kReps; ++rep)
+            for (int side = 0; side < 2; ++side) {
+                const WinTimes x = win_measure(side ? v : base, s.data(), d.data(), pairs, n, st, e0, e1);
+                t[side][0][rep] = x.one, t[side][1][rep] = x.many, t[side][2][rep] = x.fresh;
+            }
+        // the issue's two conditions: slowest repetition of the variant under
+        // the shipped form's fastest with reuse; no-reuse median not above the
+        // shipped form's slowest
+        double lo[2][3], med[2][3], hi[2][3];
+        for (int side = 0; side < 2; ++side)
+            for (int m = 0; m < 3; ++m) win_stats(t[side][m], kReps, &lo[side][m], &med[side][m], &hi[side][m]);
+        // one line per form: every repetition of the three figures, the form's
+        // and the shipped form's beside it (us per copy, in the order measured)
+        printf("{\"variant\": \"%s\", \"bytes\": %zu, \"unit_period_window\": [%u, %u, %u], \"noreuse_pairs\": %d",
+               v.name, n, 1u << v.w.unit_shift, v.w.period_mask + 1, v.w.window, pairs);
+        const char* keys[2][3] = {{"base_one", "base_x20", "base_noreuse"}, {"one", "x20", "noreuse"}};
+        for (int side = 1; side >= 0; --side)
+            for (int m = 0; m < 3; ++m) {
+                printf(", \"%s\": [", keys[side][m]);
+                for (int rep = 0; rep < kReps; ++rep) printf("%s%.1f", rep ? ", " : "", t[side][m][rep]);
+                printf("]");
+            }
+        printf(", \"reuse_gain\": %s, \"noreuse_ok\": %s, \"bad_words\": %u}\n",
+               hi[1][1] < lo[0][1] && hi[1][0] < lo[0][0] ? "true" : "false", med[1][2] <= hi[0][2] ? "true" : "false", nb);
+        fflush(stdout);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     const size_t n = argc > 1 ? strtoull(argv[1], 0, 0) : (1ull << 30);
+    if (argc > 2 && !strncmp(argv[2], "win", 3))
+        return win_lab(n, argc > 3 ? argv[3] : nullptr, argc > 4 ? argv[4] : nullptr, !strcmp(argv[2], "win2"));
     const char* only = argc > 2 ? argv[2] : nullptr;
     // optional placement offsets (argv[3] dst, argv[4] src, bytes): where the
     // two buffers sit relative to each other in the HBM channel interleave
