@@ -517,6 +517,12 @@ int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
    header of their own, which is part of this one. */
 #include "mpx_hostlink_lat.h"
 
+/* ---- sequenced payloads: every iteration of a pair loop sends its own ------ */
+/* mpx_xfer_seq, mpx_seq_expect, mpx_seq_opts and MPX_SEQ_AUTO_MAX are
+   declared, with their contract, in a header of their own, which is part of
+   this one. */
+#include "mpx_seq.h"
+
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of
    two [2^e, 2^(e+1)) splits into 16 equal buckets (<= 1/16 relative);

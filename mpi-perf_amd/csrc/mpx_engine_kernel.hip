@@ -387,10 +387,19 @@ bool armed_matches(const KernelCall& kc, int mode, int group, int peer_rank, int
 }  // namespace
 
 int run_kernel(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int group, int iters,
-               long long len, const mpx_xfer_opts* o, mpx_timing* t) {
+               long long len, const mpx_xfer_opts* o, mpx_timing* t, const u64* seq_keys) {
     const double t_call = now_s();
     KernelCall kc;
     TRY(prepare_call(ctx, me, peer, my_rank, peer_rank, mode, group, iters, len, o, &kc));
+    if (seq_keys) {
+        // a sequenced call: the same arguments and launch shape; the pushes
+        // are generated, so there is no tx to stage, and it is never traced
+        kc.a.seq = 1;
+        kc.a.seq_tx_key = seq_keys[0];
+        kc.a.seq_rx_key = seq_keys[1];
+        kc.a.stage = 0;
+        kc.a.lat = nullptr;
+    }
     const int st = launch_call(me, kc.c, [&] { return launch_xfer(kc.a, kc.grid, me.stream); });
     if (st != MPX_OK) {
         give_back(me, kc.c);

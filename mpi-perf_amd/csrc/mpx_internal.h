@@ -231,6 +231,12 @@ struct XferArgs {
     u64 go_timeout_ticks;        // armed call: how long the kernel waits for go
     LatBlock* lat;               // the rank's latency recorder (mpx_lat_enable); null =
                                  // tracing off, and then no _lat kernel is launched
+    // sequenced payloads (mpx_xfer_seq, k_xfer_seq): the pushing kernel generates
+    // iteration i's payload from seq_tx_key ^ i << 24 instead of reading tx
+    int seq;                     // 1 = launch_xfer picks the k_xfer_seq kernels
+    u64 seq_tx_key;              // mpx_pattern_key(seed, my rank, peer rank, 0): this side's sends
+    u64 seq_rx_key;              // mpx_pattern_key(seed, peer rank, my rank, 0): its receives (the
+                                 // host's expectations; no kernel compares payloads itself)
 };
 
 // LL threshold of a link.  Within one GPU the bulk path's extra hop (payload

@@ -494,7 +494,11 @@ enum { kTsEntry = 0, kTsPosted = 1, kTsFirst = 2, kTsLoop = 3 };
 
 // ANYWG: every workgroup owns an LL message of its own (k_xfer_fan_ll: one
 // link per workgroup); false: a pair's LL message is workgroup 0's.
-template <int MODE, bool ANYWG = false>
+// SEQ: where a push's bytes come from.  false: tx, the same bytes in every
+// iteration (staged in LDS, or preloaded for LL); true: generated in
+// registers from the iteration's key (mpx_xfer_seq: gen_ll, gen_units), with
+// the same stores, chunks, flags and publish schedule.
+template <int MODE, bool ANYWG = false, bool SEQ = false>
 struct Loop {
     const XferArgs& a;
     int* s_abort;      // LDS: this workgroup gave up
@@ -530,6 +534,22 @@ struct Loop {
                 w = *reinterpret_cast<const u64*>(a.tx + off);
             } else {
                 for (long long b = 0; off + b < n; ++b) w |= (u64)a.tx[off + b] << (8 * b);
+            }
+            pre[j] = w;
+        }
+    }
+
+    // SEQ: the LL payload of iteration key's send, regenerated by the lanes
+    // that own units; bytes past n are zero, as preload_ll leaves them
+    __device__ void gen_ll(long long n, u64 key) {
+#pragma unroll
+        for (int j = 0; j < kUnits; ++j) {
+            const int u = (int)threadIdx.x + j * kBlock;
+            const long long off = 8ll * u;
+            u64 w = 0;
+            if (off < n) {
+                w = fill_word(key, (u64)u);
+                if (off + 8 > n) w &= (1ull << (8 * (int)(n - off))) - 1;
             }
             pre[j] = w;
         }
@@ -620,17 +640,55 @@ struct Loop {
         else push_units<kAuxSys, STAGE>(src, dst, nv);
     }
 
+    // SEQ: the chunk's 16-B units generated instead of read: unit v of a chunk
+    // whose first 64-bit word is k0 (lo / 8) holds words k0 + 2v and k0 + 2v + 1
+    // of the iteration's pattern.  The same 4-deep batches of stores.
+    __device__ __forceinline__ v4u gen16(u64 key, u64 k) const {
+        const u64 w0 = fill_word(key, k), w1 = fill_word(key, k + 1);
+        return v4u{(unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1, (unsigned)(w1 >> 32)};
+    }
+    template <int AUX>
+    __device__ __forceinline__ void gen_units(__amdgpu_buffer_rsrc_t dst, int nv, u64 key, u64 k0) const {
+        int v = threadIdx.x;
+        for (; v + 3 * kBlock < nv; v += 4 * kBlock) {
+            const v4u r0 = gen16(key, k0 + 2 * (u64)v), r1 = gen16(key, k0 + 2 * (u64)(v + kBlock)),
+                      r2 = gen16(key, k0 + 2 * (u64)(v + 2 * kBlock)), r3 = gen16(key, k0 + 2 * (u64)(v + 3 * kBlock));
+            __builtin_amdgcn_raw_buffer_store_b128(r0, dst, v * 16, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(r1, dst, (v + kBlock) * 16, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(r2, dst, (v + 2 * kBlock) * 16, 0, AUX);
+            __builtin_amdgcn_raw_buffer_store_b128(r3, dst, (v + 3 * kBlock) * 16, 0, AUX);
+        }
+        for (; v < nv; v += kBlock)
+            __builtin_amdgcn_raw_buffer_store_b128(gen16(key, k0 + 2 * (u64)v), dst, v * 16, 0, AUX);
+    }
+
     // publish = false: the stores are issued but not drained and no flag is
     // stored (non-blocking mode publishes every a.nb_publish pushes, see k_xfer).
     // dst_base: the peer's receive slot (default: its rx).  skip (test knob
     // MPX_TEST_SKIP_PUSH): no payload stores, the flag is still published.
+    // key (SEQ): the iteration's pattern key; skip then skips generation too.
     __device__ void push_bulk(long long n, u64 seq, bool publish = true, unsigned char* dst_base = nullptr,
-                              bool skip = false) const {
+                              bool skip = false, u64 key = 0) const {
         const int w = wg();
         if (w >= a.nwg) return;
         long long lo, hi;
         chunk_of(n, &lo, &hi);
-        if (lo < hi) {
+        if constexpr (SEQ) {
+            if (lo < hi && !skip) {
+                const unsigned bytes = (unsigned)(hi - lo);
+                const __amdgpu_buffer_rsrc_t dst = rsrc((dst_base ? dst_base : a.peer_rx) + lo, bytes);
+                const int nv = (int)(bytes >> 4);
+                const u64 k0 = (u64)lo >> 3;               // lo is a multiple of 16
+                if (a.stream) gen_units<kAuxSysNt>(dst, nv, key, k0);
+                else gen_units<kAuxSys>(dst, nv, key, k0);
+                const unsigned tail = bytes & 15;          // only the last workgroup: the one or two words they fall in
+                if (threadIdx.x < tail) {
+                    const unsigned o = (unsigned)nv * 16 + threadIdx.x;
+                    const u64 wd = fill_word(key, k0 + (o >> 3));
+                    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(wd >> (8 * (o & 7))), dst, o, 0, kAuxSys);
+                }
+            }
+        } else if (lo < hi) {
             const unsigned bytes = (unsigned)(hi - lo);
             const __amdgpu_buffer_rsrc_t dst = rsrc((dst_base ? dst_base : a.peer_rx) + lo, bytes);
             const int nv = (int)(bytes >> 4);
@@ -657,9 +715,9 @@ struct Loop {
         if (threadIdx.x == 0) st_sys(&a.peer_mb->flag[a.my_slot][w], seq);
     }
 
-    __device__ void send(long long n, u64 seq, bool skip = false) const {
+    __device__ void send(long long n, u64 seq, bool skip = false, u64 key = 0) const {
         if (is_ll(n)) { if (!skip) push_ll(n, seq); else push_ll_tags_only(n, seq); }
-        else push_bulk(n, seq, true, nullptr, skip);
+        else push_bulk(n, seq, true, nullptr, skip, key);
     }
 
     // test knob: an LL message whose payload was "lost" — the tags arrive (so
@@ -1347,13 +1405,13 @@ struct LatTrace<true, ANYWG> {
 // The arguments come by value: the pull kernels then compile to the
 // instructions they had as kernels of their own, and the pushing sides load
 // their arguments once instead of at every use.
-template <int MODE, int GROUP, bool LAT>
+template <int MODE, int GROUP, bool LAT, bool SEQ = false>
 __device__ __forceinline__ void xfer_body(const XferArgs a) {
     __shared__ int s_abort;
     __shared__ u64 lds4[4];
     extern __shared__ v4u s_tx[];            // a.stage: dynamic LDS = one chunk
     if (threadIdx.x == 0) s_abort = 0;
-    Loop<MODE> L{a, &s_abort, lds4, s_tx, {}};
+    Loop<MODE, false, SEQ> L{a, &s_abort, lds4, s_tx, {}};
     LatTrace<LAT> T;
     if (!L.wait_go()) {
         if (L.last_to_finish()) L.finish_last();
@@ -1364,7 +1422,9 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
     // the size this side sends: B, or the 1-byte ack of unidir group 0
     const long long send_len = (MODE == MPX_MODE_UNIDIR && GROUP == 0) ? 1 : n;
     const bool ll_send = blockIdx.x == 0 && L.is_ll(send_len);
-    if (ll_send) L.preload_ll(send_len);
+    if constexpr (!SEQ) {
+        if (ll_send) L.preload_ll(send_len);
+    }
     u64 txs = a.tx_seq0, rxs = a.rx_seq0;
     u64 done = 0;                                       // receives completed (Status.recv_done)
     int inflight = 0;
@@ -1382,9 +1442,16 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
     const bool last_recv_wg0 = !a.check && blockIdx.x != 0;
     for (int i = 0; go && i < a.iters; ++i) {
         const bool skip = a.skip_push == i + 1;        // test knob only
+        // SEQ: this iteration's key, scalar; an LL send's units are generated
+        // here, ahead of whatever this side waits for first
+        u64 key = 0;
+        if constexpr (SEQ) {
+            key = a.seq_tx_key ^ ((u64)(unsigned)i << 24);
+            if (ll_send && !skip) L.gen_ll(send_len, key);
+        }
         if constexpr (MODE == MPX_MODE_PINGPONG) {    // mpi_perf.c:70-82
             if constexpr (GROUP == 1) {
-                L.send(n, ++txs, skip);                // Send(tx, B, tag 1)
+                L.send(n, ++txs, skip, key);           // Send(tx, B, tag 1)
                 if (i + 1 == a.iters && last_recv_wg0) break;
                 if (!L.recv(n, ++rxs, i)) break;       // Recv(rx, B, tag 2)
                 ++done;
@@ -1393,11 +1460,11 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
                 if (!L.recv(n, ++rxs, i)) break;       // Recv(rx, B, tag 1)
                 ++done;
                 if (a.check) L.check(n, i);
-                L.send(n, ++txs, skip);                // Send(tx, B, tag 2)
+                L.send(n, ++txs, skip, key);           // Send(tx, B, tag 2)
             }
         } else if constexpr (MODE == MPX_MODE_UNIDIR) {  // mpi_perf.c:132-144
             if constexpr (GROUP == 1) {
-                L.send(n, ++txs, skip);                // Send(tx, B)
+                L.send(n, ++txs, skip, key);           // Send(tx, B)
                 if (i + 1 == a.iters && last_recv_wg0) break;
                 if (!L.recv(1, ++rxs, i)) break;       // Recv(rx, 1) — the ack
                 ++done;
@@ -1406,7 +1473,7 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
                 if (!L.recv(n, ++rxs, i)) break;       // Recv(rx, B)
                 ++done;
                 if (a.check) { L.check(n, i); if (!L.grid_sync(i)) break; }
-                L.send(1, ++txs, skip);                // Send(tx, 1)
+                L.send(1, ++txs, skip, key);           // Send(tx, 1)
             }
         } else {                                       // mpi_perf.c:95-124
             // Isend + Irecv, slot `inflight`.  A receiver waits only at the
@@ -1418,7 +1485,7 @@ __device__ __forceinline__ void xfer_body(const XferArgs a) {
             // for the slot-255 push the reference leaves pending.
             const int slot = i % kNbWindow;
             L.push_bulk(n, ++txs, (i + 1) % a.nb_publish == 0 || slot == kNbWindow - 2 || i + 1 == a.iters,
-                        nullptr, skip);
+                        nullptr, skip, key);
             if (inflight == kNbWindow - 1) {
                 // Waitall(255, ...): receives of slots 0..254 (iterations
                 // i-255 .. i-1); the receive posted in slot 255 (this
@@ -1465,6 +1532,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer(XferArgs a) {
 template <int MODE, int GROUP>
 __global__ __launch_bounds__(kBlock, 4) void k_xfer_lat(XferArgs a) {
     xfer_body<MODE, GROUP, true>(a);
+}
+// mpx_xfer_seq: the same loops with every pushed payload generated from the
+// iteration's key (Loop's SEQ policy); never traced
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_seq(XferArgs a) {
+    xfer_body<MODE, GROUP, false, true>(a);
 }
 
 // The non-blocking loop in check mode (mpi_perf.c:95-124 with every payload
@@ -1514,6 +1587,62 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_nbcheck(XferArgs a) {
             if (!ok) break;
         }
         L.push_bulk(n, a.tx_seq0 + (u64)i + 1, true, L.slot_base(a.peer_rx, a.peer_ring, i), a.skip_push == i + 1);
+        if (inflight == kNbWindow - 1) {               // Waitall(255): iterations i-255 .. i-1
+            ok = L.nb_wait([&] { return next >= i; }, &next, i);
+            if (ok && w == 0) ok = L.nb_waitall(i - inflight, i, &done, &dig, fmix, &next, i);
+            inflight = 0;
+        } else {
+            ++inflight;
+        }
+    }
+    if (ok && inflight > 0) {                          // Waitall(inflight)
+        ok = L.nb_wait([&] { return next >= a.iters; }, &next, a.iters - 1);
+        if (ok && w == 0) ok = L.nb_waitall(a.iters - inflight, a.iters, &done, &dig, fmix, &next, a.iters - 1);
+    }
+    // every payload: also the receives the reference leaves pending
+    if (ok) L.nb_wait([&] { return next >= a.iters; }, &next, a.iters - 1);
+    if (w == 0 && threadIdx.x == 0) {
+        L.rdone = done;
+        L.rdig = dig;
+    }
+    if (L.last_to_finish()) L.finish_last();
+}
+
+// k_xfer_seq_nbcheck: k_xfer_nbcheck with every push generated from its
+// iteration's key (mpx_xfer_seq; Loop's SEQ policy) — the same waits, slots,
+// credits, windows and accounting, line for line.  A kernel of its own: with
+// the loop shared through an inlined function, k_xfer_nbcheck came out with
+// other SGPR spills (44 -> 46) than it has as a kernel written out.
+__global__ __launch_bounds__(kBlock, 4) void k_xfer_seq_nbcheck(XferArgs a) {
+    __shared__ int s_abort;
+    __shared__ u64 lds4[4];
+    extern __shared__ v4u s_tx[];
+    if (threadIdx.x == 0) s_abort = 0;
+    Loop<MPX_MODE_NONBLOCKING, false, true> L{a, &s_abort, lds4, s_tx, {}};
+    if (!L.wait_go()) {
+        if (L.last_to_finish()) L.finish_last();
+        return;
+    }
+    L.stamp(kTsEntry);
+    const long long n = a.len;
+    const int w = blockIdx.x;
+    const u64 fmix = mix64((u64)n);
+    const u64* credit = &a.my_mb->credit[a.peer_slot][w];
+    int next = 0, inflight = 0;
+    u64 done = 0, dig = 0;
+    L.post_receives();
+    bool ok = a.iters == 0 || L.nb_wait([&] { return threadIdx.x != 0 || L.peer_posted(); }, &next, 0);
+    L.stamp(kTsPosted);
+    for (int i = 0; i < a.iters && ok; ++i) {
+        // slot ring_slot(i) was last used by push i - S of this call: wait
+        // for its credit
+        if (i >= a.slots) {
+            const u64 want = a.tx_seq0 + (u64)(i - a.slots + 1);
+            ok = L.nb_wait([&] { return threadIdx.x != 0 || ld_sys(credit) >= want; }, &next, i);
+            if (!ok) break;
+        }
+        L.push_bulk(n, a.tx_seq0 + (u64)i + 1, true, L.slot_base(a.peer_rx, a.peer_ring, i), a.skip_push == i + 1,
+                    a.seq_tx_key ^ ((u64)(unsigned)i << 24));
         if (inflight == kNbWindow - 1) {               // Waitall(255): iterations i-255 .. i-1
             ok = L.nb_wait([&] { return next >= i; }, &next, i);
             if (ok && w == 0) ok = L.nb_waitall(i - inflight, i, &done, &dig, fmix, &next, i);
@@ -2296,6 +2425,20 @@ __global__ __launch_bounds__(kBlock) void k_account(Status* st, const u64* csum,
 hipError_t launch_xfer(const XferArgs& a, int grid, hipStream_t s) {
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
     void (*k)(XferArgs) = nullptr;
+    // a sequenced call (mpx_xfer_seq): never traced, never pulled, no LDS stage
+    if (a.seq) {
+        if (a.lat || a.pull || a.stage) return hipErrorInvalidValue;
+        switch (a.mode) {
+            case MPX_MODE_PINGPONG: k = a.group ? k_xfer_seq<MPX_MODE_PINGPONG, 1> : k_xfer_seq<MPX_MODE_PINGPONG, 0>; break;
+            case MPX_MODE_UNIDIR: k = a.group ? k_xfer_seq<MPX_MODE_UNIDIR, 1> : k_xfer_seq<MPX_MODE_UNIDIR, 0>; break;
+            case MPX_MODE_NONBLOCKING:   // both sides alike
+                k = a.check ? k_xfer_seq_nbcheck : k_xfer_seq<MPX_MODE_NONBLOCKING, 0>;
+                break;
+            default: return hipErrorInvalidValue;
+        }
+        hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    }
     // tracing on (a.lat): the blocking loops' traced instantiations; the
     // non-blocking loop has none and must not be handed a recorder
     if (a.lat) {

@@ -281,11 +281,13 @@ int check_args(mpx_ctx* ctx, int mode, const int* my_group, int my_rank, int pee
 int check_call(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, int iters, void* tx, void* rx,
                int buff_len, const mpx_xfer_opts* opts);
 int check_verdict(Rank& me, int my_rank, int groups, int per, u64 n, const uint64_t* want, mpx_timing* t, int* bad,
-                  u64* digest);
+                  u64* digest, const uint64_t* want_each = nullptr);
 
 // ---- mpx_engine_kernel.hip: the kernel engine --------------------------------
+// seq_keys (mpx_xfer_seq): {send base, receive base} of a sequenced call, which
+// runs the k_xfer_seq kernels; null: an ordinary call
 int run_kernel(mpx_ctx* ctx, Rank& me, Rank& peer, int my_rank, int peer_rank, int mode, int group, int iters,
-               long long len, const mpx_xfer_opts* o, mpx_timing* t);
+               long long len, const mpx_xfer_opts* o, mpx_timing* t, const u64* seq_keys = nullptr);
 int start_armed(Rank& me, int my_rank, int peer_rank, int mode, int group, int iters, long long len,
                 const mpx_xfer_opts* o, double t_call, mpx_timing* t);
 int disarm(Rank& me);

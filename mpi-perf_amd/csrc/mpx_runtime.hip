@@ -12,6 +12,7 @@
 //   mpx_xfer(_ex)            do_mpi_benchmark{,_nonblocking,_unidir} :66-145
 //   mpx_barrier              MPI_Barrier                          :499, :557, :579
 #include "mpx_runtime.h"
+#include "mpx_seq.h"
 
 using namespace mpx;
 
@@ -1067,8 +1068,10 @@ int check_call(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank,
 // null-stream copy would wait for every blocking stream of the device, i.e.
 // for other pairs' kernels) — which also drains whatever the caller enqueued
 // on it before, with no group at all too.
+// want_each (mpx_xfer_seq): an expectation per payload, want_each[g * per + i],
+// in want[g]'s place.
 int check_verdict(Rank& me, int my_rank, int groups, int per, u64 n, const uint64_t* want, mpx_timing* t, int* bad,
-                  u64* digest) {
+                  u64* digest, const uint64_t* want_each) {
     const size_t words = (size_t)groups * (size_t)per;
     std::vector<u64> raw(words);
     if (words) HIPCK(hipMemcpyAsync(raw.data(), me.csum, words * sizeof(u64), hipMemcpyDeviceToHost, me.stream));
@@ -1081,7 +1084,7 @@ int check_verdict(Rank& me, int my_rank, int groups, int per, u64 n, const uint6
         for (int i = 0; i < per; ++i) {
             const u64 c = raw[(size_t)g * per + i] ^ fmix;
             sum += c;
-            if (c != want[g]) ++miss;
+            if (c != (want_each ? want_each[(size_t)g * per + i] : want[g])) ++miss;
         }
         if (bad) bad[g] = miss;
         if (digest) digest[g] = sum;
@@ -1151,6 +1154,65 @@ int mpx_xfer(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, i
     const int st = mpx_xfer_ex(ctx, mode, my_group, my_rank, peer_rank, iters, tx, rx, buff_len, nullptr, &t);
     if (sec) *sec = t.wall_s;
     return st;
+}
+
+// ---------------------------------------------------------------------------
+// sequenced payloads (include/mpx_seq.h; k_xfer_seq, k_xfer_seq_nbcheck)
+// ---------------------------------------------------------------------------
+int mpx_seq_expect(uint64_t seed, int src, int dst, int iter, size_t n, uint64_t* out) {
+    if (!out) return fail(MPX_ERR_INVALID, "NULL argument");
+    if (src < 0 || src >= MPX_MAX_RANKS || dst < 0 || dst >= MPX_MAX_RANKS || iter < 0)
+        return fail(MPX_ERR_INVALID, "ranks %d/%d, iteration %d", src, dst, iter);
+    *out = seq::expect(seq::key_of(seq::key_base(seed, src, dst), iter), n);
+    return MPX_OK;
+}
+
+int mpx_xfer_seq(mpx_ctx* ctx, int mode, int my_group, int my_rank, int peer_rank, int iters, void* tx, void* rx,
+                 int buff_len, const mpx_seq_opts* opts, mpx_timing* t) {
+    if (!ctx || !opts || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    // ---- refusals: all before any GPU work ------------------------------------
+    if (ctx->engine != MPX_ENGINE_KERNEL) return fail(MPX_ERR_UNSUPPORTED, "mpx_xfer_seq: the kernel engine only");
+    if (pull_requested(nullptr))
+        return fail(MPX_ERR_UNSUPPORTED,
+                    "mpx_xfer_seq with MPX_XFER_PULL set: a pulled payload would have to be written into tx first");
+    if (opts->flags & ~MPX_XFER_STREAM)
+        return fail(MPX_ERR_INVALID, "flags %#x: only MPX_XFER_STREAM (a sequenced call reads no tx to stage or pull)",
+                    opts->flags);
+    TRY(check_args(ctx, mode, &my_group, my_rank, peer_rank, iters, buff_len));
+    const bool ack = mode == MPX_MODE_UNIDIR && my_group == 1;
+    const u64 recv_len = ack ? 1 : (u64)buff_len;   // the ack is always 1 byte (mpi_perf.c:137,142)
+    const bool check = opts->check != 0;
+    if (check && !opts->expect && (u64)iters * recv_len > MPX_SEQ_AUTO_MAX)
+        return fail(MPX_ERR_INVALID, "expect == NULL with %d x %llu B to generate on the CPU: above MPX_SEQ_AUTO_MAX (%llu)",
+                    iters, recv_len, (u64)MPX_SEQ_AUTO_MAX);
+    // a rank's state before its buffers' set-up (check_call: the checksum words and the check ring)
+    if (my_rank >= 0 && my_rank < ctx->nranks && ctx->r[my_rank].armed)
+        return fail(MPX_ERR_STATE, "rank %d holds an armed call (a sequenced call cannot be armed: start or disarm it first)",
+                    my_rank);
+    mpx_xfer_opts o{};
+    o.check = check ? 1 : 0;
+    o.flags = opts->flags;
+    o.timeout_ms = opts->timeout_ms;
+    o.nwg = opts->nwg;
+    TRY(check_call(ctx, mode, my_group, my_rank, peer_rank, iters, tx, rx, buff_len, &o));
+    Rank& me = ctx->r[my_rank];
+    Rank& peer = ctx->r[peer_rank];
+    const u64 keys[2] = {seq::key_base(opts->seed, my_rank, peer_rank), seq::key_base(opts->seed, peer_rank, my_rank)};
+    // the expectations the caller left to the library: on the CPU, before the timed call
+    std::vector<uint64_t> own;
+    const uint64_t* want = opts->expect;
+    if (check && !want) {
+        own.resize((size_t)iters);
+        for (int i = 0; i < iters; ++i) own[(size_t)i] = seq::expect(seq::key_of(keys[1], i), (size_t)recv_len);
+        want = own.data();
+    }
+    DeviceGuard g(me.dev);
+    HIPCK(g.err);
+    TRY(run_kernel(ctx, me, peer, my_rank, peer_rank, mode, my_group, iters, buff_len, &o, t, keys));
+    t->bytes = (uint64_t)buff_len * (uint64_t)iters * (mode == MPX_MODE_UNIDIR ? 1u : 2u);
+    if (!check || iters <= 0) return MPX_OK;
+    return check_verdict(me, my_rank, 1, iters, recv_len, nullptr, t, nullptr, nullptr, want);
 }
 
 int mpx_shutdown(void) {

@@ -66,7 +66,7 @@ void mpxh_print_usage(FILE *f)
 		    -g <rank->GPU list, e.g. 0,1,2,3>\n\
 		    -e <engine kernel|sdma|rccl>\n\
 		    -a <all-pairs circle-method rounds 0|1>\n\
-		    -c <checksum every payload 0|1|2 (2: seeded-pattern payloads)>\n\
+		    -c <checksum every payload 0|1|2|3 (2: seeded-pattern payloads, 3: a payload of its own per iteration)>\n\
 		    -S <min:max power-of-two message-size sweep>\n\
 		    -t <device wait timeout ms>\n\
 		    -A <launch each run's kernel before the barrier 0|1 (default 1)>\n\
@@ -311,8 +311,43 @@ static int validate_duplex(const mpxh_options *o, FILE *err)
     return 0;
 }
 
+/* -c 3 (sequenced payloads: every run is an mpx_xfer_seq call, every payload
+   checked against expectations the library generates): pair calls of the
+   kernel engine, never armed or traced */
+static int validate_seq(const mpxh_options *o, FILE *err)
+{
+    const int top = o->sweep_min > 0 ? o->sweep_max : o->buff_sz;
+    if (o->engine != 0) {
+        fprintf(err, "invalid -c 3 with -e sdma|rccl: sequenced payloads are generated by the kernel engine only\n");
+        return 1;
+    }
+    if (o->fan) {
+        fprintf(err, "invalid -c 3 with -m %d: a fan call sends its tx blocks, not sequenced payloads\n", o->fan);
+        return 1;
+    }
+    if (o->hostlink) {
+        fprintf(err, "invalid -c 3 with -H %d: a host-link call sends its tx, not sequenced payloads\n", o->hostlink);
+        return 1;
+    }
+    if (o->arm_set && o->arm) {
+        fprintf(err, "invalid -c 3 with -A 1: a sequenced call cannot be armed ahead of the barrier\n");
+        return 1;
+    }
+    if (o->lat_cap >= 0) {
+        fprintf(err, "invalid -c 3 with -L %d: sequenced calls are never traced by the latency recorder\n", o->lat_cap);
+        return 1;
+    }
+    if (o->iters > 0 && top > 0 && (unsigned long long)o->iters * (unsigned long long)top > MPXH_SEQ_AUTO_MAX) {
+        fprintf(err, "invalid -c 3 with -i %d and -b %d: more than %llu bytes of expected payloads to generate per run\n",
+                o->iters, top, MPXH_SEQ_AUTO_MAX);
+        return 1;
+    }
+    return 0;
+}
+
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
+    if (o->check == 3 && validate_seq(o, err)) return 1;
     /* -T (the host-link recorder): a -H run of the blocking loops */
     if (o->hostlink_lat_cap >= 0 && !o->hostlink) {
         fprintf(err, "invalid -T %d without -H: the host-link recorder traces host-link calls only\n", o->hostlink_lat_cap);

@@ -100,6 +100,11 @@ const char *mpxh_engine_name(int e);
 #define MPXH_FAN_ALIGN 4096
 /* -m 2: the largest -b (MPX_FAN_LL_MAX, include/mpx.h) */
 #define MPXH_FAN_LL_MAX 4096
+/* -c 3: the most bytes of expected payloads per run, -i x -b (MPX_SEQ_AUTO_MAX,
+   include/mpx_seq.h), and the run's seed: the same on both sides of a link */
+#define MPXH_SEQ_AUTO_MAX (1ull << 28)
+#define MPXH_SEQ_RUN_SEED(pattern_seed, run_idx) \
+    ((unsigned long long)(pattern_seed) + (unsigned long long)(run_idx) * 0x9E3779B97F4A7C15ull)
 /* -H: a rank's host endpoint is rank world + r of the same context */
 #define MPXH_HOSTLINK_MAX_WORLD (MPXH_MAX_RANKS / 2)
 size_t mpxh_fan_stride(int buff_len);
@@ -115,7 +120,9 @@ int mpxh_fan_peers(int world, int rank, int *peers);
    and a -b too large for world blocks (-m 2: the same, and a -b above
    MPXH_FAN_LL_MAX), and -P without -m 2; -H against -x 1, -a 1, -m, an
    explicit -A 1, -L, -d 1, -e sdma|rccl, processes mode and -w above
-   MPXH_HOSTLINK_MAX_WORLD, and -T without -H or with -X 1; then group_size, mpi_perf.c:399-403 (with -H the
+   MPXH_HOSTLINK_MAX_WORLD, and -T without -H or with -X 1; -c 3 against
+   -e sdma|rccl, -m, -H, an explicit -A 1, -L and -i x -b above
+   MPXH_SEQ_AUTO_MAX; then group_size, mpi_perf.c:399-403 (with -H the
    job is the 2 * world ranks: the GPU ranks and their endpoints).
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides

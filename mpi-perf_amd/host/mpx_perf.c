@@ -415,7 +415,10 @@ static void *rank_main(void *arg)
             mpx_xfer_opts xo;
             memset(&xo, 0, sizeof xo);
             xo.timeout_ms = (uint32_t)opt.timeout_ms;
-            if (opt.check && !opt.use_dotnet) {
+            /* -c 3: every run is a sequenced call (mpx_xfer_seq): the library
+               generates the expected payloads itself, from the run's seed */
+            const int seq = opt.check == 3 && !opt.use_dotnet;
+            if (opt.check && !opt.use_dotnet && !seq) {
                 /* expected payloads: the peer's tx, read after every fill */
                 uint64_t s, s1;
                 checksum_tx(r, (size_t)B, &s);
@@ -429,7 +432,7 @@ static void *rank_main(void *arg)
             /* SDMA engine: capture this (mode, peer, B)'s graph chunks now, not
                inside the timed call (the reference's timer brackets only the
                loop, mpi_perf.c:501-533) */
-            if (!opt.use_dotnet && !opt.hostlink)
+            if (!opt.use_dotnet && !opt.hostlink && !seq)
                 MPX_CHECK(mpx_xfer_prepare(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo));
             /* -L: every run's distribution is its own (before the arm: an
                armed rank's recorder cannot be touched) */
@@ -438,7 +441,7 @@ static void *rank_main(void *arg)
             /* -A 1: the run's kernel is launched now and started by the
                mpx_xfer_ex after the barrier (MPI_Start of a persistent
                request), so the launch is not inside the timed loop */
-            if (!opt.use_dotnet && opt.arm && !opt.hostlink) /* (a host-link call cannot be armed) */
+            if (!opt.use_dotnet && opt.arm && !opt.hostlink && !seq) /* (a host-link or sequenced call cannot be armed) */
                 MPX_CHECK(mpx_xfer_arm(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo));
             start_barrier(); /* MPI_Barrier, mpi_perf.c:499 */
             const double t_start = wtime();
@@ -455,6 +458,13 @@ static void *rank_main(void *arg)
                 MPX_CHECK(mpx_host_xfer(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo, &tm));
             } else if (opt.hostlink) {
                 MPX_CHECK(mpx_xfer_hostlink(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
+            } else if (seq) {
+                mpx_seq_opts so;
+                memset(&so, 0, sizeof so);
+                so.seed = MPXH_SEQ_RUN_SEED(MPX_PATTERN_SEED, run_idx);
+                so.check = 1;
+                so.timeout_ms = (uint32_t)opt.timeout_ms;
+                MPX_CHECK(mpx_xfer_seq(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &so, &tm));
             } else {
                 MPX_CHECK(mpx_xfer_ex(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
             }
@@ -494,7 +504,7 @@ static void *rank_main(void *arg)
                             tm.nwg,
                             (unsigned long long)tm.check_iters, tm.check_failures, run_idx,
                             (unsigned long long)tm.recv_done, (unsigned long long)tm.recv_digest,
-                            (opt.arm && opt.engine == MPX_ENGINE_KERNEL && !opt.hostlink) ? "armed" : "inline", rccl_build);
+                            (opt.arm && opt.engine == MPX_ENGINE_KERNEL && !opt.hostlink && !seq) ? "armed" : "inline", rccl_build);
                 }
                 if (lat && files.lat_fp) {
                     mpx_lat l;

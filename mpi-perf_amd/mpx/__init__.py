@@ -78,6 +78,21 @@ class XferOpts(C.Structure):
     ]
 
 
+SEQ_AUTO_MAX = 1 << 28   # MPX_SEQ_AUTO_MAX: bytes xfer_seq generates on the CPU when expect is None
+
+
+class SeqOpts(C.Structure):
+    """mpx_seq_opts (include/mpx_seq.h)"""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("check", C.c_int32),
+        ("flags", C.c_int32),
+        ("timeout_ms", C.c_uint32),
+        ("nwg", C.c_int32),
+        ("expect", C.POINTER(C.c_uint64)),
+    ]
+
+
 class HostBox(C.Structure):
     """hostlink::HostBox (csrc/mpx_hostlink.h): one direction of a host
     endpoint's mailbox, rows indexed by the GPU peer's rank"""
@@ -253,6 +268,9 @@ _SIGS = {
                                        C.POINTER(Timing)]),
     "mpx_host_checksum": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "mpx_hostlink_ll_max": (C.c_int, []),
+    "mpx_xfer_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_int, C.POINTER(SeqOpts), C.POINTER(Timing)]),
+    "mpx_seq_expect": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint64)]),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mpx_rccl_get_unique_id": (C.c_int, [C.c_void_p]),
     "mpx_rccl_init_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -334,6 +352,14 @@ def host_checksum(data, offset: int = 0, n: int | None = None) -> int:
 def hostlink_ll_max() -> int:
     """mpx_hostlink_ll_max: the host link's LL threshold in force (MPX_HOSTLINK_LL)"""
     return lib().mpx_hostlink_ll_max()
+
+
+def seq_expect(seed: int, src: int, dst: int, it: int, n: int) -> int:
+    """mpx_seq_expect: the checksum of the n-byte payload rank src sends rank
+    dst in iteration `it` of a sequenced call (xfer_seq), on the CPU"""
+    out = C.c_uint64()
+    check(lib().mpx_seq_expect(seed & 0xFFFFFFFFFFFFFFFF, src, dst, it, n, C.byref(out)), "mpx_seq_expect")
+    return out.value
 
 
 def shutdown() -> None:
@@ -447,6 +473,29 @@ class Context:
             st = self.L.mpx_xfer_ex(self.h, mode, group, my_rank, peer_rank, iters, C.c_void_p(tx.ptr),
                                     C.c_void_p(rx.ptr), length, C.byref(o), C.byref(t))
         check(st, "mpx_xfer_ex")
+        return t
+
+    def xfer_seq(self, mode: int, group: int, my_rank: int, peer_rank: int, iters: int, tx: Buffer, rx: Buffer,
+                 length: int, seed: int, check_payload: bool = False, expect=None, timeout_ms: int = 0, nwg: int = 0,
+                 stream: bool = False) -> Timing:
+        """mpx_xfer_seq: the pair loop with a generated payload of its own in
+        every iteration.  expect: check mode, the checksum of each of the
+        `iters` payloads this side receives (None: the library computes
+        them).  A failing call raises MpxError carrying .timing"""
+        arr = None
+        if expect is not None:
+            expect = list(expect)
+            arr = (C.c_uint64 * max(len(expect), 1))(*expect)
+        o = SeqOpts(seed=seed & 0xFFFFFFFFFFFFFFFF, check=1 if check_payload else 0, flags=XFER_STREAM if stream else 0,
+                    timeout_ms=timeout_ms, nwg=nwg,
+                    expect=C.cast(arr, C.POINTER(C.c_uint64)) if arr is not None else None)
+        t = Timing()
+        st = self.L.mpx_xfer_seq(self.h, mode, group, my_rank, peer_rank, iters, C.c_void_p(tx.ptr), C.c_void_p(rx.ptr),
+                                 length, C.byref(o), C.byref(t))
+        if st != OK:
+            e = MpxError(st, "mpx_xfer_seq")
+            e.timing = t
+            raise e
         return t
 
     def fan(self, my_rank: int, peers, iters: int, tx: Buffer, rx: Buffer, block_len: int, stride: int,
