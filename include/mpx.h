@@ -523,6 +523,11 @@ int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
    this one. */
 #include "mpx_seq.h"
 
+/* ---- sequenced fan payloads: a payload per (sender, receiver, iteration) ---- */
+/* mpx_xfer_fan_seq and mpx_fan_seq_opts are declared, with their contract, in
+   a header of their own, which is part of this one. */
+#include "mpx_fan_seq.h"
+
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of
    two [2^e, 2^(e+1)) splits into 16 equal buckets (<= 1/16 relative);

@@ -3,6 +3,7 @@
 // armed call (mpx_xfer_arm, start_armed, disarm), the fan call (mpx_xfer_fan)
 // and the host-link call (run_hostlink_kernel) all go through.
 #include "mpx_runtime.h"
+#include "mpx_seq.h"
 
 #include <algorithm>
 
@@ -589,11 +590,22 @@ int mpx_fan_width(int nranks, int block_len, int same_device, int nwg) {
     return w > 0 ? w : -1;
 }
 
-int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int iters, void* tx, void* rx,
-                 int block_len, size_t stride, const mpx_fan_opts* opts, mpx_timing* t, mpx_fan_link* links) {
+namespace {
+// what a sequenced fan call (mpx_xfer_fan_seq) adds to an ordinary one
+struct FanSeq {
+    u64 seed;                 // the job's seed: link k's pushes carry mpx_pattern_key(seed, me, peers[k], i)
+    const uint64_t* expect;   // check mode: [npeers * iters], or null: computed here on the CPU
+};
+
+// One call path for mpx_xfer_fan (sq == null) and mpx_xfer_fan_seq: the same
+// checks in the same order, table, lifecycle and results.  A sequenced call
+// differs in the kernels' payload source (FanArgs.seq, seq_seed), in a
+// per-payload expectation array for the verdict, and in never being traced.
+int fan_call(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int iters, void* tx, void* rx, int block_len,
+             size_t stride, const mpx_fan_opts* opts, mpx_timing* t, mpx_fan_link* links, const FanSeq* sq) {
     if (!ctx || !peers || !t) return fail(MPX_ERR_INVALID, "NULL argument");
     memset(t, 0, sizeof *t);
-    const double t_call = now_s();
+    double t_call = now_s();
     // ---- argument checks: all before any GPU work ---------------------------
     if (my_rank < 0 || my_rank >= ctx->nranks) return fail(MPX_ERR_INVALID, "rank %d", my_rank);
     if (npeers < 1 || npeers > ctx->nranks - 1)
@@ -607,7 +619,7 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
         return fail(MPX_ERR_INVALID, "flags %#x: only MPX_XFER_STREAM or MPX_FAN_LL", opts->flags);
     const bool ll = opts && (opts->flags & MPX_FAN_LL);
     const bool check = opts && opts->check;
-    if (check && !opts->expect_checksum) return fail(MPX_ERR_INVALID, "check mode needs expect_checksum[npeers]");
+    if (check && !sq && !opts->expect_checksum) return fail(MPX_ERR_INVALID, "check mode needs expect_checksum[npeers]");
     bool seen[MPX_MAX_RANKS] = {};
     int top = my_rank;
     for (int k = 0; k < npeers; ++k) {
@@ -618,7 +630,8 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
         seen[p] = true;
         if (p > top) top = p;
     }
-    if (ctx->engine != MPX_ENGINE_KERNEL) return fail(MPX_ERR_UNSUPPORTED, "mpx_xfer_fan: the kernel engine only");
+    if (ctx->engine != MPX_ENGINE_KERNEL)
+        return fail(MPX_ERR_UNSUPPORTED, "%s: the kernel engine only", sq ? "mpx_xfer_fan_seq" : "mpx_xfer_fan");
     TRY(check_rank_state(ctx, my_rank, tx, rx, peers, npeers));
     Rank& me = ctx->r[my_rank];
     if (me.armed) return fail(MPX_ERR_STATE, "rank %d holds an armed call (start or disarm it first)", my_rank);
@@ -653,6 +666,28 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
         return fail(MPX_ERR_INVALID, "rank %d: a fan grid of %lld workgroups exceeds %d (narrow the links: nwg, MPX_FAN_WG)",
                     my_rank, sum, kFanMaxGrid);
     }
+    // a sequenced call's expectations the caller left to the library: on the
+    // CPU (csrc/mpx_seq.h), before the timed part of the call
+    std::vector<uint64_t> own;
+    const uint64_t* want_each = nullptr;
+    if (sq && check) {
+        want_each = sq->expect;
+        if (!want_each) {
+            const u64 total = (u64)npeers * (u64)iters * (u64)block_len;
+            if (total > MPX_SEQ_AUTO_MAX)
+                return fail(MPX_ERR_INVALID,
+                            "expect == NULL with %d x %d x %d B to generate on the CPU: above MPX_SEQ_AUTO_MAX (%llu)", npeers,
+                            iters, block_len, (u64)MPX_SEQ_AUTO_MAX);
+            own.resize((size_t)npeers * (size_t)iters);
+            for (int k = 0; k < npeers; ++k) {
+                const u64 base = seq::key_base(sq->seed, peers[k], my_rank);
+                for (int i = 0; i < iters; ++i)
+                    own[(size_t)k * iters + i] = seq::expect(seq::key_of(base, i), (size_t)block_len);
+            }
+            want_each = own.data();
+            t_call = now_s();
+        }
+    }
     // ---- set-up ----------------------------------------------------------------
     DeviceGuard g(me.dev);
     HIPCK(g.err);
@@ -677,6 +712,8 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
     a.stream = (opts && (opts->flags & MPX_XFER_STREAM)) ? 1 : 0;
     a.nb_publish = nb_publish();
     a.skip_push = knobs.skip_push;
+    a.seq = sq ? 1 : 0;
+    a.seq_seed = sq ? sq->seed : 0;
     Call c;
     c.my_rank = my_rank;
     c.iters = iters;
@@ -713,7 +750,8 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
             la.lag_ticks = (u64)knobs.lag_us * 100ull;   // s_memrealtime: 100 MHz
         }
         // the link recorder (mpx_fan_lat_enable): launch_fan_ll then picks the traced kernels
-        la.lat = me.fan_lat.on ? me.fan_lat.base : nullptr;
+        // (a sequenced call runs untraced whatever the recorder's state, and leaves its contents)
+        la.lat = me.fan_lat.on && !sq ? me.fan_lat.base : nullptr;
         la.lat_stride = me.fan_lat.stride();
     }
     const int lst = launch_call(me, c, [&] { return ll ? launch_fan_ll(la, me.stream) : launch_fan(a, grid, me.stream); });
@@ -738,7 +776,7 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
     int bad[MPX_MAX_RANKS] = {};
     u64 digest[MPX_MAX_RANKS] = {};
     const int verdict = check_verdict(me, my_rank, check ? npeers : 0, iters, (u64)block_len,
-                                      check ? opts->expect_checksum : nullptr, t, bad, digest);
+                                      check && !sq ? opts->expect_checksum : nullptr, t, bad, digest, want_each);
     if (verdict != MPX_OK && verdict != MPX_ERR_CHECK) return verdict;
     for (int k = 0; links && k < npeers; ++k) {
         const FanLink& l = me.fan_host->link[k];
@@ -750,6 +788,25 @@ int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int it
         links[k].device_s = (fin.t_entry && l.t_end >= fin.t_entry) ? (double)(l.t_end - fin.t_entry) * 1e-8 : 0;
     }
     return verdict;
+}
+}  // namespace
+
+int mpx_xfer_fan(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int iters, void* tx, void* rx,
+                 int block_len, size_t stride, const mpx_fan_opts* opts, mpx_timing* t, mpx_fan_link* links) {
+    return fan_call(ctx, my_rank, npeers, peers, iters, tx, rx, block_len, stride, opts, t, links, nullptr);
+}
+
+// sequenced fan payloads (include/mpx_fan_seq.h; k_xfer_fan's and k_xfer_fan_ll's GEN instantiations)
+int mpx_xfer_fan_seq(mpx_ctx* ctx, int my_rank, int npeers, const int* peers, int iters, void* tx, void* rx,
+                     int block_len, size_t stride, const mpx_fan_seq_opts* opts, mpx_timing* t, mpx_fan_link* links) {
+    if (!ctx || !peers || !opts || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    mpx_fan_opts o{};
+    o.check = opts->check ? 1 : 0;
+    o.flags = opts->flags;   // (fan_call refuses any bit other than MPX_XFER_STREAM / MPX_FAN_LL)
+    o.timeout_ms = opts->timeout_ms;
+    o.nwg = opts->nwg;
+    const FanSeq sq{opts->seed, opts->expect};
+    return fan_call(ctx, my_rank, npeers, peers, iters, tx, rx, block_len, stride, &o, t, links, &sq);
 }
 
 }  // extern "C"

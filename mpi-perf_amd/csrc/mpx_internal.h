@@ -323,6 +323,11 @@ struct FanArgs {
     long long len;            // block_len
     int iters, nlinks, my_slot;
     int check, stream, nb_publish, skip_push;
+    // sequenced payloads (mpx_xfer_fan_seq): the pushes of link k generate iteration
+    // i's block from mpx_pattern_key(seq_seed, my_slot, link k's peer, i) instead of
+    // reading tx; the kernels derive the key, so FanLink stays as it is
+    int seq;                  // 1 = launch_fan / launch_fan_ll pick the generating instantiations
+    u64 seq_seed;
 };
 
 // The lock-step LL fan exchange (MPX_FAN_LL, k_xfer_fan_ll): one workgroup

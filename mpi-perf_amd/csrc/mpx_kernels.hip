@@ -2117,7 +2117,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_hostlink_duplex(XferArgs a) {
 // the compiler takes 106 SGPRs there, as for every k_xfer kernel; with the
 // cap it keeps 38 scalar values in VGPR lanes instead.  No scratch either way
 // (DESIGN.md "Fan exchange").
-template <bool CHECK>
+// GEN: where a push's bytes come from (mpx_xfer_fan_seq).  false: the link's tx
+// block; true: chunk w of iteration i's pattern under the link's key, generated
+// in registers (Loop::gen_units, the tail bytes as push_bulk's SEQ branch) —
+// tx is not touched; waits, drain, flag, credit, checksum, poison and both
+// ends are the same lines.  The key is derived here from the call's seed, this
+// rank and the link's peer, so FanLink and FanTable stay as they are.  Figures
+// of the GEN instantiations: DESIGN.md "Sequenced fan payloads".
+template <bool CHECK, bool GEN = false>
 __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan(FanArgs f) {
     __shared__ int s_abort;
     __shared__ u64 lds4[4];
@@ -2153,6 +2160,12 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
     u64* credit_out = &lk.peer_mb->credit[f.my_slot][w];
     const u64* flag_in = &f.my_mb->flag[lk.peer][w];
     const u64* credit_in = &f.my_mb->credit[lk.peer][w];
+    // GEN: mpx_pattern_key(seed, me, peer, 0), uniform per workgroup; the chunk's first 64-bit word
+    u64 key0 = 0, k0 = 0;
+    if constexpr (GEN) {
+        key0 = f.seq_seed ^ ((u64)(unsigned)f.my_slot << 56) ^ ((u64)(unsigned)lk.peer << 48);
+        k0 = (u64)lo >> 3;                              // lo is a multiple of 16
+    }
 
     // bounded one-lane poll of a word a peer writes
     auto wait_ge = [&](const u64* p, u64 want, int iter) -> bool {
@@ -2178,10 +2191,21 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
             if (!ok) break;
         }
         if (bytes && f.skip_push != i + 1) {           // (test knob: this payload is "lost")
-            L.push_units_aux<false>(reinterpret_cast<const v4u*>(src), dst, nv);
-            if (threadIdx.x < tail) {
-                const unsigned o = (unsigned)nv * 16 + threadIdx.x;
-                __builtin_amdgcn_raw_buffer_store_b8(src[o], dst, o, 0, kAuxSys);
+            if constexpr (GEN) {
+                const u64 key = key0 ^ ((u64)(unsigned)i << 24);
+                if (f.stream) L.template gen_units<kAuxSysNt>(dst, nv, key, k0);
+                else L.template gen_units<kAuxSys>(dst, nv, key, k0);
+                if (threadIdx.x < tail) {                  // the one or two words the tail bytes fall in
+                    const unsigned o = (unsigned)nv * 16 + threadIdx.x;
+                    const u64 wd = fill_word(key, k0 + (o >> 3));
+                    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(wd >> (8 * (o & 7))), dst, o, 0, kAuxSys);
+                }
+            } else {
+                L.push_units_aux<false>(reinterpret_cast<const v4u*>(src), dst, nv);
+                if (threadIdx.x < tail) {
+                    const unsigned o = (unsigned)nv * 16 + threadIdx.x;
+                    __builtin_amdgcn_raw_buffer_store_b8(src[o], dst, o, 0, kAuxSys);
+                }
             }
         }
         if (CHECK || (i + 1) % f.nb_publish == 0 || i + 1 == f.iters) {
@@ -2303,9 +2327,13 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
 // one changes the callers' register allocation (k_xfer_fan: 73 -> 75 VGPRs),
 // so the body stands here in the kernel, and k_xfer_fan keeps end-of-call code
 // of its own (DESIGN.md "Link recorder").
+// GEN (mpx_xfer_fan_seq): no preload; iteration i's units are generated from
+// the link's key (Loop::gen_ll) before every push_ll.  A skipped push stays
+// push_ll_tags_only.  Never traced: there is no LAT && GEN instantiation.
 // ---------------------------------------------------------------------------
-template <bool CHECK, bool LAT>
+template <bool CHECK, bool LAT, bool GEN = false>
 __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) void k_xfer_fan_ll(FanLLArgs q) {
+    static_assert(!(LAT && GEN), "a sequenced LL fan call is never traced");
     __shared__ int s_abort;
     __shared__ u64 lds4[4];
     if (threadIdx.x == 0) s_abort = 0;
@@ -2327,12 +2355,14 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
     x.done_token = f.done_token;
     x.iters = f.iters;
     x.ll_max = MPX_FAN_LL_MAX;
-    Loop<MPX_MODE_PINGPONG, true> L{x, &s_abort, lds4, nullptr, {}};
+    Loop<MPX_MODE_PINGPONG, true, GEN> L{x, &s_abort, lds4, nullptr, {}};
     __syncthreads();
     L.stamp(kTsEntry);
     const u64 tx0 = lk.tx_seq0, rx0 = lk.rx_seq0;
     if (threadIdx.x == 0) st_sys(&lk.peer_mb->posted[f.my_slot], lk.call);
-    L.preload_ll(n);
+    u64 key0 = 0;   // GEN: mpx_pattern_key(seed, me, peer, 0)
+    if constexpr (GEN) key0 = f.seq_seed ^ ((u64)(unsigned)f.my_slot << 56) ^ ((u64)(unsigned)lk.peer << 48);
+    else L.preload_ll(n);
     bool ok = f.iters > 0;
     if (ok) {
         if (threadIdx.x == 0) {
@@ -2358,8 +2388,12 @@ __global__ __launch_bounds__(kBlock, 4) __attribute__((amdgpu_num_sgpr(80))) voi
     for (int i = 0; ok && i < f.iters; ++i) {
         const u64 s = tx0 + (u64)i + 1, r = rx0 + (u64)i + 1;
         const unsigned out = (unsigned)(s & 1) * kFanLLHalf, in = (unsigned)(r & 1) * kFanLLHalf;
-        if (f.skip_push == i + 1) L.push_ll_tags_only(n, s, out);   // (test knob: this payload is "lost")
-        else L.push_ll(n, s, out);
+        if (f.skip_push == i + 1) {
+            L.push_ll_tags_only(n, s, out);                        // (test knob: this payload is "lost")
+        } else {
+            if constexpr (GEN) L.gen_ll(n, key0 ^ ((u64)(unsigned)i << 24));
+            L.push_ll(n, s, out);
+        }
         if (q.lag_ticks && k == q.lag_link && i == f.iters / 2) {   // (test knob)
             if (threadIdx.x == 0) {
                 const u64 t0 = now_ticks();
@@ -2511,7 +2545,9 @@ hipError_t launch_hostlink_duplex(const XferArgs& a, hipStream_t s) {
 hipError_t launch_fan(const FanArgs& a, int grid, hipStream_t s) {
     if (grid < 1 || grid > kFanMaxGrid) return hipErrorInvalidValue;
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
-    void (*k)(FanArgs) = a.check ? k_xfer_fan<true> : k_xfer_fan<false>;
+    // a sequenced call (mpx_xfer_fan_seq): the generating instantiations
+    void (*k)(FanArgs) = a.seq ? (a.check ? k_xfer_fan<true, true> : k_xfer_fan<false, true>)
+                               : (a.check ? k_xfer_fan<true> : k_xfer_fan<false>);
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
@@ -2523,6 +2559,11 @@ hipError_t launch_fan_ll(const FanLLArgs& a, hipStream_t s) {
     if (a.lat && a.lat_stride < sizeof(LatBlock)) return hipErrorInvalidValue;
     void (*k)(FanLLArgs) = a.lat ? (a.f.check ? k_xfer_fan_ll<true, true> : k_xfer_fan_ll<false, true>)
                                  : (a.f.check ? k_xfer_fan_ll<true, false> : k_xfer_fan_ll<false, false>);
+    // a sequenced call (mpx_xfer_fan_seq) is never traced: it has no traced instantiation
+    if (a.f.seq) {
+        if (a.lat) return hipErrorInvalidValue;
+        k = a.f.check ? k_xfer_fan_ll<true, false, true> : k_xfer_fan_ll<false, false, true>;
+    }
     hipLaunchKernelGGL(k, dim3((unsigned)a.f.nlinks), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }

@@ -74,6 +74,7 @@ void mpxh_print_usage(FILE *f)
 		    -m <1: every run is one fan exchange, each rank with all others at once (kernel engine)>\n\
 		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n\
 		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n\
+		    -Q <1: with -m 1|2, every run is one sequenced fan call: a payload per (src, dst, iteration); -c 0|1>\n\
 		    -H <1|2: each of the -w ranks is a GPU rank paired with a CPU endpoint across the host link;>\n\
 		       <1: the GPU rank sends first (-u 1: device to host), 2: the endpoint does (kernel engine, threads)>\n\
 		    -X <1: with -H, every run is the full-duplex non-blocking loop across the host link (both directions at once)>\n\
@@ -86,7 +87,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:T:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:T:Q:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -142,6 +143,9 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
             o->fan_lat_cap = (int)v;
             break;
         }
+        case 'Q': /* (0 or 1; anything else is refused by mpxh_validate, after -c 3 -m's own refusal) */
+            o->fan_seq = !strcmp(optarg, "0") ? 0 : !strcmp(optarg, "1") ? 1 : -1;
+            break;
         case 'T': {
             char *end = NULL;
             const long v = strtol(optarg, &end, 10);
@@ -345,9 +349,42 @@ static int validate_seq(const mpxh_options *o, FILE *err)
     return 0;
 }
 
+/* -Q 1 (sequenced fan payloads: every run of a -m 1|2 job is one
+   mpx_xfer_fan_seq call): tx is not sent, the call is never traced, and with
+   -c 1 the library generates every expected payload on the CPU */
+static int validate_fan_seq(const mpxh_options *o, int world, FILE *err)
+{
+    const int top = o->sweep_min > 0 ? o->sweep_max : o->buff_sz;
+    if (o->fan_seq != 1) {
+        fprintf(err, "invalid -Q: its value is 0 or 1\n");
+        return 1;
+    }
+    if (!o->fan) {
+        fprintf(err, "invalid -Q 1 without -m: sequenced fan payloads are a fan run's (-c 3 is the pair loops')\n");
+        return 1;
+    }
+    if (o->check == 2) {
+        fprintf(err, "invalid -Q 1 with -c 2: a sequenced fan call does not send tx\n");
+        return 1;
+    }
+    if (o->fan_lat_cap >= 0) {
+        fprintf(err, "invalid -Q 1 with -P %d: sequenced fan calls are never traced by the link recorder\n", o->fan_lat_cap);
+        return 1;
+    }
+    if (o->check == 1 && world > 1 && o->iters > 0 && top > 0 &&
+        (unsigned long long)(world - 1) * (unsigned long long)o->iters * (unsigned long long)top > MPXH_SEQ_AUTO_MAX) {
+        fprintf(err,
+                "invalid -Q 1 -c 1 with %d peers, -i %d and -b %d: more than %llu bytes of expected payloads to generate per run\n",
+                world - 1, o->iters, top, MPXH_SEQ_AUTO_MAX);
+        return 1;
+    }
+    return 0;
+}
+
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
     if (o->check == 3 && validate_seq(o, err)) return 1;
+    if (o->fan_seq && validate_fan_seq(o, world, err)) return 1;
     /* -T (the host-link recorder): a -H run of the blocking loops */
     if (o->hostlink_lat_cap >= 0 && !o->hostlink) {
         fprintf(err, "invalid -T %d without -H: the host-link recorder traces host-link calls only\n", o->hostlink_lat_cap);

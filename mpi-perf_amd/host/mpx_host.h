@@ -71,6 +71,10 @@ typedef struct mpxh_options {
                                            iteration's latency on both ends of
                                            the host link (mpx_hostlink_lat_*),
                                            lat-*.csv; -1 (default) = off      */
+    int fan_seq;                    /* -Q  1: with -m 1|2, every run is one
+                                           sequenced fan call (mpx_xfer_fan_seq):
+                                           a payload per (src, dst, iteration);
+                                           a malformed value reads as -1      */
 } mpxh_options;
 
 /* parse status */
@@ -87,7 +91,7 @@ enum {
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:m:P:H:X:T:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:P:H:X:T:Q:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -122,7 +126,10 @@ int mpxh_fan_peers(int world, int rank, int *peers);
    explicit -A 1, -L, -d 1, -e sdma|rccl, processes mode and -w above
    MPXH_HOSTLINK_MAX_WORLD, and -T without -H or with -X 1; -c 3 against
    -e sdma|rccl, -m, -H, an explicit -A 1, -L and -i x -b above
-   MPXH_SEQ_AUTO_MAX; then group_size, mpi_perf.c:399-403 (with -H the
+   MPXH_SEQ_AUTO_MAX; -Q against a value other than 0 or 1, a run without
+   -m, -c 2, -P and, with -c 1, (world - 1) x -i x -b above
+   MPXH_SEQ_AUTO_MAX (-c 3 with -m keeps its own refusal, which comes
+   first); then group_size, mpi_perf.c:399-403 (with -H the
    job is the 2 * world ranks: the GPU ranks and their endpoints).
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides

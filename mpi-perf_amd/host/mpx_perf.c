@@ -25,7 +25,9 @@
  * -a 1 every run is one round of the circle-method all-pairs schedule; with
  * -m 1 every run is one fan exchange: every rank with all the others at once
  * (mpx_xfer_fan, kernel engine), any world >= 2; -m 2 the same as a lock-step
- * exchange of LL granules (MPX_FAN_LL, -b up to 4096).  With -H 1|2 (threads
+ * exchange of LL granules (MPX_FAN_LL, -b up to 4096); -Q 1 beside either
+ * makes every run a sequenced fan call (mpx_xfer_fan_seq: a generated payload
+ * per sender, receiver and iteration; tx is not sent).  With -H 1|2 (threads
  * mode, kernel engine) each of the -w ranks is a GPU rank paired with a CPU
  * endpoint of its own across the host link (rank world + r, its loop on a
  * thread of its own: mpx_xfer_hostlink / mpx_host_xfer); the job is then
@@ -563,8 +565,9 @@ static void *rank_main_fan(void *arg)
     for (int si = 0; si < nsizes; ++si) {
         const int B = sizes[si];
         const size_t stride = mpxh_fan_stride(B);
-        /* the compat fill: 'a' + src % 26 in every block */
-        if (opt.check != 2)
+        /* the compat fill: 'a' + src % 26 in every block (-Q 1 sends no tx, and a
+           peer's checksum of it is not needed either) */
+        if (opt.check != 2 && !opt.fan_seq)
             MPX_CHECK(mpx_fill(ctx, dev_of[r], tx_of[r], (size_t)world * stride, MPX_FILL_BYTE, 'a' + r % 26));
         for (long long run_idx = 0; opt.num_runs == -1 || run_idx < opt.num_runs; run_idx++) {
             if (opt.check == 2)
@@ -578,7 +581,7 @@ static void *rank_main_fan(void *arg)
             memset(&fo, 0, sizeof fo);
             fo.timeout_ms = (uint32_t)opt.timeout_ms;
             if (opt.fan == 2) fo.flags = MPX_FAN_LL; /* -m 2: per link a lock-step exchange of LL granules */
-            if (opt.check) {
+            if (opt.check && !opt.fan_seq) {
                 /* the world x world block checksums, read after every fill */
                 uint64_t mine[MPXH_MAX_RANKS] = {0};
                 for (int d = 0; d < world; ++d)
@@ -595,7 +598,18 @@ static void *rank_main_fan(void *arg)
             mpx_timing tm;
             mpx_fan_link links[MPXH_MAX_RANKS];
             memset(&tm, 0, sizeof tm);
-            MPX_CHECK(mpx_xfer_fan(ctx, r, np, peers, opt.iters, tx_of[r], rx_of[r], B, stride, &fo, &tm, links));
+            if (opt.fan_seq) {
+                /* -Q 1: a payload per (src, dst, iteration) under the run's seed; -c 1
+                   checks every one against expectations the library generates */
+                mpx_fan_seq_opts so;
+                memset(&so, 0, sizeof so);
+                so.seed = MPXH_SEQ_RUN_SEED(MPX_PATTERN_SEED, run_idx);
+                so.check = opt.check ? 1 : 0;
+                so.flags = fo.flags;
+                so.timeout_ms = fo.timeout_ms;
+                MPX_CHECK(mpx_xfer_fan_seq(ctx, r, np, peers, opt.iters, tx_of[r], rx_of[r], B, stride, &so, &tm, links));
+            } else
+                MPX_CHECK(mpx_xfer_fan(ctx, r, np, peers, opt.iters, tx_of[r], rx_of[r], B, stride, &fo, &tm, links));
             const double my_time = wtime() - t_start; /* mpi_perf.c:532-533 */
 
             if (run_idx > 0) { /* mpi_perf.c:545-555, every rank */

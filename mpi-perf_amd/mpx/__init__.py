@@ -121,6 +121,18 @@ class FanOpts(C.Structure):
     ]
 
 
+class FanSeqOpts(C.Structure):
+    """mpx_fan_seq_opts (include/mpx_fan_seq.h)"""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("check", C.c_int32),
+        ("flags", C.c_int32),
+        ("timeout_ms", C.c_uint32),
+        ("nwg", C.c_int32),
+        ("expect", C.POINTER(C.c_uint64)),
+    ]
+
+
 class FanLink(C.Structure):
     """mpx_fan_link: one link's results of a fan call"""
     _fields_ = [
@@ -271,6 +283,8 @@ _SIGS = {
     "mpx_xfer_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                C.c_int, C.POINTER(SeqOpts), C.POINTER(Timing)]),
     "mpx_seq_expect": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "mpx_xfer_fan_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_size_t, C.POINTER(FanSeqOpts), C.POINTER(Timing), C.POINTER(FanLink)]),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mpx_rccl_get_unique_id": (C.c_int, [C.c_void_p]),
     "mpx_rccl_init_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -522,6 +536,37 @@ class Context:
         out = [links[k].as_dict() for k in range(n)]
         if st != OK:
             e = MpxError(st, "mpx_xfer_fan")
+            e.timing, e.links = t, out
+            raise e
+        return t, out
+
+    def xfer_fan_seq(self, my_rank: int, peers, iters: int, tx: Buffer, rx: Buffer, block_len: int, stride: int,
+                     seed: int, check_payload: bool = False, expect=None, timeout_ms: int = 0, nwg: int = 0,
+                     stream: bool = False, ll: bool = False):
+        """mpx_xfer_fan_seq: the fan exchange (arguments as fan) with a
+        generated payload per (sender, receiver, iteration); tx is not sent.
+        expect: check mode, the checksums of the payloads this rank receives,
+        expect[k * iters + i] for peers[k] (None: the library computes them).
+        Returns (Timing, [link dicts]); a failing call raises MpxError
+        carrying .timing and .links as far as they were filled."""
+        peers = list(peers)
+        n = len(peers)
+        arr = (C.c_int * max(n, 1))(*peers)
+        exp = None
+        if expect is not None:
+            expect = list(expect)
+            exp = (C.c_uint64 * max(len(expect), 1))(*expect)
+        flags = (XFER_STREAM if stream else 0) | (XFER_FAN_LL if ll else 0)
+        o = FanSeqOpts(seed=seed & 0xFFFFFFFFFFFFFFFF, check=1 if check_payload else 0, flags=flags,
+                       timeout_ms=timeout_ms, nwg=nwg,
+                       expect=C.cast(exp, C.POINTER(C.c_uint64)) if exp is not None else None)
+        t = Timing()
+        links = (FanLink * max(n, 1))()
+        st = self.L.mpx_xfer_fan_seq(self.h, my_rank, n, arr, iters, C.c_void_p(tx.ptr), C.c_void_p(rx.ptr), block_len,
+                                     stride, C.byref(o), C.byref(t), links)
+        out = [links[k].as_dict() for k in range(n)]
+        if st != OK:
+            e = MpxError(st, "mpx_xfer_fan_seq")
             e.timing, e.links = t, out
             raise e
         return t, out
