@@ -401,7 +401,7 @@ hipError_t launch_hostlink_duplex(const XferArgs& a, hipStream_t s);
 // loaded with the default cache policy, so that it stays in the 256 MiB
 // Infinity Cache for the next copy of the same buffer, when
 //     (b / unit) % period < window        (unit in blocks, period and window in units)
-// and nontemporal, as every store, otherwise.  unit and period are powers of
+// and nontemporal otherwise (the stores: k_copy_win).  unit and period are powers of
 // two: the kernel's test is a shift, a mask and a compare.  on = false is
 // k_copy, the kernel without the choice.
 struct CopyWindow {

@@ -128,27 +128,34 @@ __global__ __launch_bounds__(kBlock) void k_copy(const v4u* __restrict__ src, v4
 
 // ---------------------------------------------------------------------------
 // k_copy_win: launch_copy's form of k_copy (one 16-B unit per lane, one step
-// per block, nontemporal stores) with the load's cache policy chosen per
-// workgroup (CopyWindow, mpx_internal.h).  Workgroup b copies 4 KiB block b;
-// a kept block, ((b >> shift) & mask) < units, loads with the default policy
-// so that it stays in the Infinity Cache for the next copy of src.  The
-// branch is uniform.  The kept load is a buffer load, the streamed one a
-// nontemporal pointer load: two loads of one pointer that differ only in the
-// hint are merged into one plain load under __restrict__, which drops the hint.
+// per block) with the load's cache policy chosen per workgroup (CopyWindow,
+// mpx_internal.h).  Workgroup b copies 4 KiB block b; a kept block,
+// ((b >> shift) & mask) < units, loads with the default policy so that it
+// stays in the Infinity Cache for the next copy of src.  The branch is
+// uniform.  The kept load is a buffer load, the streamed one a nontemporal
+// pointer load: two loads of one pointer that differ only in the hint are
+// merged into one plain load under __restrict__, which drops the hint.
+// Every store is a buffer store with sc1 | nt: 7 us of 317 faster per GiB
+// than the nontemporal pointer store, with and without reuse, and the window
+// stays resident under it (DESIGN.md "The streamed side's policy";
+// profiles/copy_window_keep_lab.jsonl).  Write-through, and the kernel's end
+// releases every store as before: no fence.  tests/test_copy_window_policy.py
+// reads the two constants here and the modifiers in the emitted code.
 // ---------------------------------------------------------------------------
+constexpr int kCopyWinKeptAux = 0;     // kept loads: the default policy
+constexpr int kCopyWinStoreAux = 18;   // every store: sc1 | nt
 __global__ __launch_bounds__(kBlock) void k_copy_win(const v4u* __restrict__ src, v4u* __restrict__ dst, size_t n16,
                                                     unsigned tail, unsigned shift, unsigned mask, unsigned units) {
-    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (((blockIdx.x >> shift) & mask) < units) {
-        // the descriptor covers this block's whole units only: a lane past n16 loads nothing
-        const size_t left = n16 - (size_t)blockIdx.x * kBlock;   // > 0: the grid is ceil(n16 / kBlock)
-        const unsigned bytes = left < (size_t)kBlock ? (unsigned)left * 16 : kBlock * 16;
-        const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rsrc(src + (size_t)blockIdx.x * kBlock, bytes),
-                                                            threadIdx.x * 16, 0, 0);
-        if (i < n16) st16<true>(dst + i, r);
-    } else if (i < n16) {
-        st16<true>(dst + i, ld16<true>(src + i));
-    }
+    const size_t first = (size_t)blockIdx.x * kBlock, i = first + threadIdx.x;
+    // the descriptors cover this block's whole units only: a lane past n16 loads and stores nothing
+    const size_t left = n16 - first;   // >= 0: the grid is ceil(n16 / kBlock), or 1 where n16 is 0
+    const unsigned bytes = left < (size_t)kBlock ? (unsigned)left * 16 : kBlock * 16;
+    v4u r = {0, 0, 0, 0};
+    if (((blockIdx.x >> shift) & mask) < units)
+        r = __builtin_amdgcn_raw_buffer_load_b128(rsrc(src + first, bytes), threadIdx.x * 16, 0, kCopyWinKeptAux);
+    else if (i < n16)
+        r = ld16<true>(src + i);
+    __builtin_amdgcn_raw_buffer_store_b128(r, rsrc(dst + first, bytes), threadIdx.x * 16, 0, kCopyWinStoreAux);
     if (blockIdx.x == 0 && threadIdx.x < tail) {   // the tail bytes, as k_copy
         const unsigned char* s8 = reinterpret_cast<const unsigned char*>(src + n16);
         unsigned char* d8 = reinterpret_cast<unsigned char*>(dst + n16);
