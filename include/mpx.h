@@ -528,6 +528,11 @@ int mpx_lat_raw(mpx_ctx *ctx, int rank, uint64_t *stamps, int cap, int *n);
    a header of their own, which is part of this one. */
 #include "mpx_fan_seq.h"
 
+/* ---- sequenced payloads on the host link: the endpoint's tx changes too ----- */
+/* mpx_xfer_hostlink_seq and mpx_host_xfer_seq are declared, with their
+   contract, in a header of their own, which is part of this one. */
+#include "mpx_hostlink_seq.h"
+
 /* The histogram's buckets, one definition for host and device.  Log-linear:
    v < 32 ticks is its own bucket (exact below 320 ns); above, each power of
    two [2^e, 2^(e+1)) splits into 16 equal buckets (<= 1/16 relative);

@@ -9,6 +9,8 @@
 
 #include "mpx_hostlink.h"
 
+#include <vector>
+
 using namespace mpx;
 
 namespace mpx {
@@ -157,12 +159,47 @@ int mpx_host_buffers(mpx_ctx* ctx, int rank, void** tx, void** rx) {
     return MPX_OK;
 }
 
-int mpx_xfer_hostlink(mpx_ctx* ctx, int mode, int my_group, int my_rank, int host_rank, int iters, void* tx, void* rx,
-                      int buff_len, const mpx_xfer_opts* opts, mpx_timing* t) {
-    if (!ctx || !t) return fail(MPX_ERR_INVALID, "NULL argument");
-    memset(t, 0, sizeof *t);
-    const double t_call = now_s();
-    TRY(check_hostlink(ctx, mode, my_group, my_rank, host_rank, iters, buff_len, opts));
+namespace {
+
+// A sequenced host-link call (include/mpx_hostlink_seq.h) beside the ordinary
+// one's options: the link's two key bases and, in check mode, the checksum
+// of every payload this side receives.
+struct SeqCall {
+    u64 tx_key, rx_key;
+    const uint64_t* want;
+};
+
+// The refusals a sequenced call adds to check_hostlink's, and the ordinary
+// options it runs under (no flag: nothing reads tx, so nothing is staged)
+int check_hostlink_seq(mpx_ctx* ctx, int mode, int group, int gpu_rank, int host_rank, int iters, int buff_len,
+                       const mpx_seq_opts* so, mpx_xfer_opts* o) {
+    if (so->flags)
+        return fail(MPX_ERR_INVALID, "flags %#x: a sequenced host-link call takes none (it reads no tx to stage)", so->flags);
+    *o = mpx_xfer_opts{};
+    o->check = so->check ? 1 : 0;
+    o->timeout_ms = so->timeout_ms;
+    o->nwg = so->nwg;
+    TRY(check_hostlink(ctx, mode, group, gpu_rank, host_rank, iters, buff_len, o));
+    const bool ack = mode == MPX_MODE_UNIDIR && group == 1;   // group: the caller's
+    const u64 recv_len = ack ? 1 : (u64)buff_len;
+    if (so->check && !so->expect && (u64)iters * recv_len > MPX_SEQ_AUTO_MAX)
+        return fail(MPX_ERR_INVALID, "expect == NULL with %d x %llu B to generate on the CPU: above MPX_SEQ_AUTO_MAX (%llu)",
+                    iters, recv_len, (u64)MPX_SEQ_AUTO_MAX);
+    return MPX_OK;
+}
+
+// expect == NULL: the expectations on the CPU, before the timed part of the call
+const uint64_t* seq_expectations(const mpx_seq_opts* so, u64 rx_key, int iters, u64 recv_len, std::vector<uint64_t>* own) {
+    if (!so->check || so->expect) return so->expect;
+    own->resize((size_t)(iters > 0 ? iters : 0));
+    for (int i = 0; i < iters; ++i) (*own)[(size_t)i] = seq::expect(seq::key_of(rx_key, i), (size_t)recv_len);
+    return own->data();
+}
+
+// the GPU side of a host-link call, ordinary (sq == nullptr) or sequenced;
+// the arguments are checked
+int gpu_hostlink(mpx_ctx* ctx, int mode, int my_group, int my_rank, int host_rank, int iters, void* tx, void* rx,
+                 int buff_len, const mpx_xfer_opts* opts, const SeqCall* sq, double t_call, mpx_timing* t) {
     Rank& me = ctx->r[my_rank];
     const Rank& host = ctx->r[host_rank];
     if (!tx || !rx || tx != me.tx || rx != me.rx)
@@ -202,11 +239,17 @@ int mpx_xfer_hostlink(mpx_ctx* ctx, int mode, int my_group, int my_rank, int hos
     a.ll_max = mpx_hostlink_ll_max();
     a.skip_push = test_knobs().skip_push;
     // the host-link recorder (mpx_hostlink_lat_enable): launch_hostlink then picks the traced kernels
-    a.lat = me.hostlink_lat.on ? me.hostlink_lat.block(host_rank) : nullptr;
+    a.lat = (me.hostlink_lat.on && !sq) ? me.hostlink_lat.block(host_rank) : nullptr;
+    // a sequenced call: k_hostlink_gen, never traced (the recorder's blocks stay as they are)
+    if (sq) {
+        a.seq = 1;
+        a.seq_tx_key = sq->tx_key;
+        a.seq_rx_key = sq->rx_key;
+    }
     const bool ll_send = send_len <= a.ll_max, ll_recv = recv_len <= a.ll_max;
     const int grid = (ll_send && ll_recv) ? 1 : a.nwg;
     // bulk pushes read tx from LDS when one workgroup's chunk fits, as a pair's
-    if (!(opts && (opts->flags & MPX_XFER_NOSTAGE)) && !ll_send && send_len > 0) {
+    if (!sq && !(opts && (opts->flags & MPX_XFER_NOSTAGE)) && !ll_send && send_len > 0) {
         int per_block = 0;
         if (hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, me.dev) != hipSuccess) per_block = 0;
         const long long chunk = (((send_len + a.nwg - 1) / a.nwg) + 15) & ~15ll;
@@ -215,16 +258,16 @@ int mpx_xfer_hostlink(mpx_ctx* ctx, int mode, int my_group, int my_rank, int hos
     TRY(run_hostlink_kernel(me, my_rank, host_rank, a, grid, len <= a.ll_max, t_call, t));
     t->bytes = (uint64_t)buff_len * (uint64_t)iters * (unidir ? 1u : 2u);
     if (!check || iters <= 0) return MPX_OK;
+    if (sq) return check_verdict(me, my_rank, 1, iters, (u64)recv_len, nullptr, t, nullptr, nullptr, sq->want);
     const bool ack = unidir && my_group == 1;
     const uint64_t want = ack ? opts->expect_ack : opts->expect_checksum;
     return check_verdict(me, my_rank, 1, iters, (u64)recv_len, &want, t, nullptr, nullptr);
 }
 
-int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_rank, int iters, int buff_len,
-                  const mpx_xfer_opts* opts, mpx_timing* t) {
-    if (!ctx || !t) return fail(MPX_ERR_INVALID, "NULL argument");
-    memset(t, 0, sizeof *t);
-    TRY(check_hostlink(ctx, mode, my_group, peer_rank, host_rank, iters, buff_len, opts));
+// the endpoint's side, ordinary (sq == nullptr) or sequenced, on the calling
+// thread; the arguments are checked
+int host_side(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_rank, int iters, int buff_len,
+              const mpx_xfer_opts* opts, const SeqCall* sq, mpx_timing* t) {
     Rank& me = ctx->r[host_rank];
     if (me.broken) return fail(MPX_ERR_STATE, "host endpoint %d: a previous transfer timed out", host_rank);
     const TestKnobs knobs = test_knobs();
@@ -252,12 +295,19 @@ int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_
     c.skip_push = knobs.skip_push;
     c.lag_iter = knobs.host_lag_iter;
     c.lag_us = knobs.host_lag_us;
-    // the endpoint's recorder (mpx_hostlink_lat_enable): the block of the GPU peer
-    if (me.host_lat_on)
+    if (sq) {
+        c.seq_tx = me.tx;
+        c.seq_tx_key = sq->tx_key;
+        c.expect_each = sq->want;
+        c.seq_stale = knobs.seq_stale;
+    }
+    // the endpoint's recorder (mpx_hostlink_lat_enable): the block of the GPU peer;
+    // a sequenced call is never traced
+    if (me.host_lat_on && !sq)
         c.lat = reinterpret_cast<hostlink::LatRec*>(me.host_lat + (size_t)peer_rank * hostlink::lat_rec_bytes(me.host_lat_cap));
     hostlink::Result r;
     const double t0 = now_s();
-    const int rc = c.lat ? hostlink::run_loop<true>(c, &r) : hostlink::run(c, &r);
+    const int rc = sq ? hostlink::run_seq(c, &r) : c.lat ? hostlink::run_loop<true>(c, &r) : hostlink::run(c, &r);
     t->wall_s = now_s() - t0;
     t->device_s = 0;
     t->launches = 0;
@@ -279,6 +329,65 @@ int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_
         return fail(MPX_ERR_CHECK, "host endpoint %d: %d of %llu received payloads failed the checksum", host_rank,
                     r.check_failures, (unsigned long long)r.check_iters);
     return MPX_OK;
+}
+
+}  // namespace
+
+int mpx_xfer_hostlink(mpx_ctx* ctx, int mode, int my_group, int my_rank, int host_rank, int iters, void* tx, void* rx,
+                      int buff_len, const mpx_xfer_opts* opts, mpx_timing* t) {
+    if (!ctx || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    const double t_call = now_s();
+    TRY(check_hostlink(ctx, mode, my_group, my_rank, host_rank, iters, buff_len, opts));
+    return gpu_hostlink(ctx, mode, my_group, my_rank, host_rank, iters, tx, rx, buff_len, opts, nullptr, t_call, t);
+}
+
+int mpx_host_xfer(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_rank, int iters, int buff_len,
+                  const mpx_xfer_opts* opts, mpx_timing* t) {
+    if (!ctx || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    TRY(check_hostlink(ctx, mode, my_group, peer_rank, host_rank, iters, buff_len, opts));
+    return host_side(ctx, mode, my_group, host_rank, peer_rank, iters, buff_len, opts, nullptr, t);
+}
+
+// ---- sequenced payloads on the host link (include/mpx_hostlink_seq.h) -----------
+// The ordinary call's two sides with the payload of iteration i generated
+// from the link's key: k_hostlink_gen on the GPU, run_seq() on the endpoint.
+
+int mpx_xfer_hostlink_seq(mpx_ctx* ctx, int mode, int my_group, int my_rank, int host_rank, int iters, void* tx, void* rx,
+                          int buff_len, const mpx_seq_opts* opts, mpx_timing* t) {
+    if (!ctx || !opts || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    const double t_call = now_s();
+    mpx_xfer_opts o;
+    TRY(check_hostlink_seq(ctx, mode, my_group, my_rank, host_rank, iters, buff_len, opts, &o));
+    // (before the expectations are generated: every refusal comes before any work)
+    const Rank& me = ctx->r[my_rank];
+    if (!tx || !rx || tx != me.tx || rx != me.rx)
+        return fail(MPX_ERR_INVALID, "tx/rx are not rank %d's attached buffers", my_rank);
+    if (me.armed)
+        return fail(MPX_ERR_STATE, "rank %d holds an armed call (a sequenced call cannot be armed: start or disarm it first)",
+                    my_rank);
+    if (me.broken) return fail(MPX_ERR_STATE, "rank %d: a previous transfer timed out", my_rank);
+    const u64 recv_len = (mode == MPX_MODE_UNIDIR && my_group == 1) ? 1 : (u64)buff_len;
+    SeqCall sq{seq::key_base(opts->seed, my_rank, host_rank), seq::key_base(opts->seed, host_rank, my_rank), nullptr};
+    std::vector<uint64_t> own;
+    sq.want = seq_expectations(opts, sq.rx_key, iters, recv_len, &own);
+    return gpu_hostlink(ctx, mode, my_group, my_rank, host_rank, iters, tx, rx, buff_len, &o, &sq, t_call, t);
+}
+
+int mpx_host_xfer_seq(mpx_ctx* ctx, int mode, int my_group, int host_rank, int peer_rank, int iters, int buff_len,
+                      const mpx_seq_opts* opts, mpx_timing* t) {
+    if (!ctx || !opts || !t) return fail(MPX_ERR_INVALID, "NULL argument");
+    memset(t, 0, sizeof *t);
+    mpx_xfer_opts o;
+    TRY(check_hostlink_seq(ctx, mode, my_group, peer_rank, host_rank, iters, buff_len, opts, &o));
+    if (ctx->r[host_rank].broken) return fail(MPX_ERR_STATE, "host endpoint %d: a previous transfer timed out", host_rank);
+    const u64 recv_len = (mode == MPX_MODE_UNIDIR && my_group == 1) ? 1 : (u64)buff_len;
+    SeqCall sq{seq::key_base(opts->seed, host_rank, peer_rank), seq::key_base(opts->seed, peer_rank, host_rank), nullptr};
+    std::vector<uint64_t> own;
+    sq.want = seq_expectations(opts, sq.rx_key, iters, recv_len, &own);
+    return host_side(ctx, mode, my_group, host_rank, peer_rank, iters, buff_len, &o, &sq, t);
 }
 
 // ---- the host-link recorder (include/mpx_hostlink_lat.h) -----------------------

@@ -24,6 +24,8 @@
 
 // mpx_lat_bucket and MPX_LAT_BUCKETS: one definition for host and device (plain C)
 #include "../../include/mpx.h"
+// the sequenced payloads' pattern and checksum (run_loop's SEQ form)
+#include "mpx_seq.h"
 
 #if defined(__x86_64__) || defined(__i386__)
 #include <immintrin.h>
@@ -172,6 +174,11 @@ struct Call {
     int lag_iter = -1;         // test knob (host_lag): the iteration before whose first step
     long long lag_us = 0;      //   the endpoint busy-waits lag_us; -1 = off
     LatRec* lat = nullptr;     // the block of the GPU peer (run_traced); nullptr = untraced
+    // a sequenced call (run_seq; include/mpx_hostlink_seq.h)
+    unsigned char* seq_tx = nullptr;        // the endpoint's tx, writable: a bulk send's payload is written here
+    uint64_t seq_tx_key = 0;                // seq::key_base(seed, endpoint, gpu): this side's sends
+    const uint64_t* expect_each = nullptr;  // check: [iters] checksums of the payloads this side receives
+    int seq_stale = 0;         // test knob: 1 + the iteration whose send repeats the payload before it
 };
 struct Result {
     uint64_t recv_done = 0, recv_digest = 0, check_iters = 0;
@@ -206,6 +213,22 @@ inline void send_ll(const Call& c, long long n, uint64_t seq, bool lose) {
         uint32_t w = 0;
         const long long off = 4ll * g;
         if (!lose && off < n) memcpy(&w, c.tx + off, (size_t)(n - off < 4 ? n - off : 4));
+        __atomic_store_n(&row[g], tag | w, __ATOMIC_RELEASE);
+    }
+}
+// CPU -> GPU, LL, sequenced: the same granules packed from the generated words
+// of the pattern `key`; tx is not touched
+inline void send_ll_gen(const Call& c, long long n, uint64_t push, uint64_t key, bool lose) {
+    uint64_t* row = c.mb->out.ll[c.gpu];
+    const uint64_t tag = (uint64_t)ll_tag(push) << 32;
+    const int ng = 2 * ll_units(n);
+    for (int g = 0; g < ng; ++g) {
+        uint32_t w = 0;
+        const long long off = 4ll * g;
+        if (!lose && off < n) {
+            w = (uint32_t)(seq::fill_word(key, (uint64_t)(g >> 1)) >> (32 * (g & 1)));
+            if (n - off < 4) w &= (1u << (8 * (int)(n - off))) - 1;
+        }
         __atomic_store_n(&row[g], tag | w, __ATOMIC_RELEASE);
     }
 }
@@ -305,7 +328,17 @@ struct Trace<true> {
 // has returned, check and poison included: one clock_gettime per iteration.
 // A call that times out leaves the block as the loop left it (undefined until
 // reset).  LAT = false reads the clock only where its waits always did.
-template <bool LAT>
+//   SEQ: a sequenced call (run_seq).  Send i carries P(seed, endpoint, gpu, i,
+// send_len), the pattern of seq::key_of(c.seq_tx_key, i): an LL send packs its
+// granules from the generated words, a bulk send writes the pattern into
+// c.seq_tx[0 : send_len) and then says "tx holds message k" as ever.  That
+// write is the one thing the ordinary loop never does, and what makes it safe
+// is the loop's own order: send_bulk returns only after every chunk's credit,
+// so when send i + 1 writes tx every load of send i has been answered.  This
+// is the invariant a sequenced call puts under test — a credit taken early, or
+// a pull served from a stale copy, now costs bytes the GPU's check can see.
+// Receive i is compared with c.expect_each[i].
+template <bool LAT, bool SEQ = false>
 inline int run_loop(const Call& c, Result* r) {
     using namespace detail;
     *r = Result{};
@@ -323,6 +356,21 @@ inline int run_loop(const Call& c, Result* r) {
     }
     auto send = [&](int i) {
         ++txs;
+        if constexpr (SEQ) {
+            const bool lose = !(unidir && c.group == 0) && c.skip_push == i + 1;
+            // test knob (seq_stale): this send repeats the payload before it —
+            // an LL send packs key i - 1, a bulk send leaves tx as it is; the
+            // first send of a call has no predecessor and sends what tx held
+            const bool stale = c.seq_stale == i + 1;
+            if (send_len <= c.ll_max) {
+                if (stale && i == 0) send_ll(c, send_len, txs, lose);
+                else send_ll_gen(c, send_len, txs, seq::key_of(c.seq_tx_key, stale ? i - 1 : i), lose);
+                return true;
+            }
+            // strictly after the credits of send i - 1 (above): tx is quiet
+            if (!stale) seq::pattern(c.seq_tx, (size_t)send_len, seq::key_of(c.seq_tx_key, i));
+            return send_bulk(c, w, txs);
+        }
         if (send_len <= c.ll_max) {
             send_ll(c, send_len, txs, !(unidir && c.group == 0) && c.skip_push == i + 1);   // (never an ack)
             return true;
@@ -337,7 +385,7 @@ inline int run_loop(const Call& c, Result* r) {
             const uint64_t got = checksum(c.rx, (size_t)recv_len);
             r->recv_digest += got;
             ++r->check_iters;
-            if (got != want) ++r->check_failures;
+            if (got != (SEQ ? c.expect_each[i] : want)) ++r->check_failures;
             if (i + 1 != c.iters) poison(c.rx, (size_t)recv_len, i, recv_len <= c.ll_max);   // the last payload stays
         }
         return true;
@@ -362,6 +410,8 @@ inline int run_loop(const Call& c, Result* r) {
 }
 // the untraced entry point (mpx_host_xfer calls run_loop<true> when c.lat is set)
 inline int run(const Call& c, Result* r) { return run_loop<false>(c, r); }
+// a sequenced call's (mpx_host_xfer_seq): never traced, c.lat is not read
+inline int run_seq(const Call& c, Result* r) { return run_loop<false, true>(c, r); }
 
 // The endpoint's side of the reference's non-blocking loop (mpi_perf.c:85-125)
 // on the calling thread — the full-duplex loop of include/mpx_hostlink_duplex.h;

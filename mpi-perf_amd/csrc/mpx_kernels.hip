@@ -16,6 +16,8 @@
 //               CPU endpoint across PCIe (mpx_xfer_hostlink): the same pushes,
 //               and bulk receives pulled from the endpoint's pinned tx
 //   k_hostlink_lat  the same loop traced per iteration (mpx_hostlink_lat_*)
+//   k_hostlink_gen  the same loop with every push generated from its
+//               iteration's key (mpx_xfer_hostlink_seq), untraced
 //   k_fill      tx fill (memset 'a'/'b', mpi_perf.c:244-251, or a seeded pattern)
 //   k_checksum  order-independent 64-bit payload checksum
 //   k_signal / k_wait   one-lane flag store / bounded poll (SDMA engine)
@@ -1828,7 +1830,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_pull_lat(XferArgs a) {
 // side that pushes first, else kTsEntry); the one clock read at the bottom of
 // iteration i is t[i+1] and, for i = 0, the kTsFirst stamp.  k_xfer_hostlink
 // is the LAT = false wrapper, k_hostlink_lat the other.
-template <int MODE, int GROUP, bool LAT>
+// SEQ: a sequenced call (mpx_xfer_hostlink_seq; Loop's SEQ policy): every send
+// is generated in registers from its iteration's key, a.seq_tx_key ^ i << 24 —
+// an LL send's units by gen_ll in place of the one preload_ll, a bulk send's
+// by push_bulk's generating branch — so tx is never read and nothing is
+// staged in LDS (a.stage = 0).  The receives are the same code: what they
+// must find is the caller's to say (check_verdict's per-payload form).
+// k_hostlink_gen is that wrapper; there is no traced form.
+template <int MODE, int GROUP, bool LAT, bool SEQ = false>
 __device__ __forceinline__ void hostlink_body(const XferArgs a) {
     static_assert(MODE == MPX_MODE_PINGPONG || MODE == MPX_MODE_UNIDIR, "the blocking loops only");
     // statics of 48 bytes: the dynamic region (the staged tx chunk) stays 16-byte aligned
@@ -1840,7 +1849,7 @@ __device__ __forceinline__ void hostlink_body(const XferArgs a) {
         s_w[4] = 0;
     }
     __syncthreads();
-    Loop<MODE> L{a, s_abort, s_w, s_tx, {}, &s_w[4]};
+    Loop<MODE, false, SEQ> L{a, s_abort, s_w, s_tx, {}, &s_w[4]};
     L.stamp(kTsEntry);
     const long long n = a.len;
     constexpr bool sends_n = MODE != MPX_MODE_UNIDIR || GROUP == 1;   // else the 1-byte ack
@@ -1848,7 +1857,9 @@ __device__ __forceinline__ void hostlink_body(const XferArgs a) {
     const long long send_len = sends_n ? n : 1, recv_len = recvs_n ? n : 1;
     const bool ll_send = L.is_ll(send_len), ll_recv = L.is_ll(recv_len);
     const bool wg0 = blockIdx.x == 0;
-    if (wg0 && ll_send) L.preload_ll(send_len);
+    if constexpr (!SEQ) {
+        if (wg0 && ll_send) L.preload_ll(send_len);
+    }
     u64 txs = a.tx_seq0, rxs = a.rx_seq0, done = 0;
     // workgroup 0 saw it in host memory: tell the others; they wait for that
     auto relay = [&](int word, u64 v) {
@@ -1872,6 +1883,13 @@ __device__ __forceinline__ void hostlink_body(const XferArgs a) {
     auto send = [&](int i) {
         ++txs;
         const bool lose = sends_n && a.skip_push == i + 1;   // test knob: a B-byte payload, never an ack
+        // SEQ: this iteration's key, scalar; an LL send's units (the ack's one
+        // byte too) are generated here, ahead of the wait for the landed chunks
+        u64 key = 0;
+        if constexpr (SEQ) {
+            key = a.seq_tx_key ^ ((u64)(unsigned)i << 24);
+            if (wg0 && ll_send && !lose) L.gen_ll(send_len, key);
+        }
         if (ll_send) {
             // a side that received a bulk payload answers once every chunk is in:
             // the chunks of the receives it has completed — i + 1 of them where it
@@ -1882,7 +1900,7 @@ __device__ __forceinline__ void hostlink_body(const XferArgs a) {
             if (!lose) L.push_ll(send_len, txs);
             else L.push_ll_tags_only(send_len, txs);
         } else {
-            L.push_bulk(send_len, txs, true, nullptr, lose);
+            L.push_bulk(send_len, txs, true, nullptr, lose, key);
         }
         return true;
     };
@@ -1942,6 +1960,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_xfer_hostlink(XferArgs a) {
 template <int MODE, int GROUP>
 __global__ __launch_bounds__(kBlock, 4) void k_hostlink_lat(XferArgs a) {
     hostlink_body<MODE, GROUP, true>(a);
+}
+// mpx_xfer_hostlink_seq: the same loop with every pushed payload generated
+// from its iteration's key; never traced
+template <int MODE, int GROUP>
+__global__ __launch_bounds__(kBlock, 4) void k_hostlink_gen(XferArgs a) {
+    hostlink_body<MODE, GROUP, false, true>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -2523,6 +2547,17 @@ hipError_t launch_hostlink(const XferArgs& a, int grid, hipStream_t s) {
         return hipErrorInvalidValue;
     (void)hipGetLastError();   // drop a stale error of an earlier, ignored call
     void (*k)(XferArgs) = nullptr;
+    // a sequenced call (mpx_xfer_hostlink_seq): never traced, no LDS stage
+    if (a.seq) {
+        if (a.lat || a.stage) return hipErrorInvalidValue;
+        switch (a.mode) {
+            case MPX_MODE_PINGPONG: k = a.group ? k_hostlink_gen<MPX_MODE_PINGPONG, 1> : k_hostlink_gen<MPX_MODE_PINGPONG, 0>; break;
+            case MPX_MODE_UNIDIR: k = a.group ? k_hostlink_gen<MPX_MODE_UNIDIR, 1> : k_hostlink_gen<MPX_MODE_UNIDIR, 0>; break;
+            default: return hipErrorInvalidValue;
+        }
+        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    }
     switch (a.mode) {
         case MPX_MODE_PINGPONG:
             // the host-link recorder on (a.lat): the traced instantiations

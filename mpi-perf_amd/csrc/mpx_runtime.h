@@ -260,6 +260,7 @@ struct TestKnobs {
     bool no_posted = false, no_pull_wait = false;
     int host_lag_iter = -1;        // host_lag=<iter>:<us>: a host endpoint stalls before that iteration
     long long host_lag_us = 0;
+    int seq_stale = 0;             // seq_stale=<k>: an endpoint's k-th sequenced send repeats the payload before it
     int fail_launch = -1;
     bool fail_copy = false;
 };

@@ -238,6 +238,13 @@ CopyChoice copy_choice() {
 //   host_lag=i:us   a host endpoint busy-waits `us` before its first step of
 //                   iteration i of every ping-pong or unidir call (mpx_host_xfer):
 //                   the stalled iteration both ends' host-link recorders must find
+//   seq_stale=k     the k-th send (1-based) of every sequenced host-link call
+//                   of a host endpoint (mpx_host_xfer_seq) repeats the payload
+//                   of the send before it: a bulk send leaves tx unwritten, an
+//                   LL send packs the key of iteration k - 2; for k = 1 it sends
+//                   what tx held.  The GPU side's check must fail at exactly
+//                   iteration k - 1 — the negative control of "every pulled
+//                   payload is fresh"
 //   fail_launch=r   rank r's kernel-engine calls fail before their kernel is
 //                   enqueued (after take_numbers took their numbers): the
 //                   rollback test of give_back (mpx_engine_kernel.hip)
@@ -274,6 +281,7 @@ TestKnobs test_knobs() {
         else if (!item.compare(0, 9, "host_lag=")) {
             if (sscanf(item.c_str() + 9, "%d:%lld", &k.host_lag_iter, &k.host_lag_us) != 2) k.host_lag_iter = -1;
         }
+        else if (!item.compare(0, 10, "seq_stale=")) k.seq_stale = atoi(item.c_str() + 10);
         else if (!item.compare(0, 12, "fail_launch=")) k.fail_launch = atoi(item.c_str() + 12);
         else if (item == "fail_copy") k.fail_copy = true;
         pos = end + 1;

@@ -75,6 +75,7 @@ void mpxh_print_usage(FILE *f)
 		       <2: the same as a lock-step exchange of LL granules, -b up to 4096 (MPX_FAN_LL)>\n\
 		    -P <raw-cap: with -m 2, record every link's per-iteration exchange latency, lat-*.csv>\n\
 		    -Q <1: with -m 1|2, every run is one sequenced fan call: a payload per (src, dst, iteration); -c 0|1>\n\
+		    -K <1: with -H 1|2, every run is a sequenced host-link call on both ends: a payload per iteration; -c 0|1>\n\
 		    -H <1|2: each of the -w ranks is a GPU rank paired with a CPU endpoint across the host link;>\n\
 		       <1: the GPU rank sends first (-u 1: device to host), 2: the endpoint does (kernel engine, threads)>\n\
 		    -X <1: with -H, every run is the full-duplex non-blocking loop across the host link (both directions at once)>\n\
@@ -87,7 +88,7 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
     int opt;
     optind = 1;
     opterr = 0;
-    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:T:Q:")) != -1) {
+    while ((opt = getopt(argc, argv, ":f:n:d:p:i:b:u:h:r:l:x:w:e:a:c:S:t:g:A:L:m:P:H:X:T:Q:K:")) != -1) {
         switch (opt) {
         case 'f': strncpy(o->group1_hostfile, optarg, MPXH_MAX_HOST - 1); break;
         case 'n': o->group_size = atoi(optarg); break;
@@ -145,6 +146,9 @@ int mpxh_parse_args(mpxh_options *o, int argc, char **argv)
         }
         case 'Q': /* (0 or 1; anything else is refused by mpxh_validate, after -c 3 -m's own refusal) */
             o->fan_seq = !strcmp(optarg, "0") ? 0 : !strcmp(optarg, "1") ? 1 : -1;
+            break;
+        case 'K': /* (0 or 1; anything else is refused by mpxh_validate) */
+            o->hostlink_seq = !strcmp(optarg, "0") ? 0 : !strcmp(optarg, "1") ? 1 : -1;
             break;
         case 'T': {
             char *end = NULL;
@@ -381,10 +385,47 @@ static int validate_fan_seq(const mpxh_options *o, int world, FILE *err)
     return 0;
 }
 
+/* -K 1 (sequenced host-link payloads: every run of a -H job is an
+   mpx_xfer_hostlink_seq / mpx_host_xfer_seq call): the blocking loops only,
+   never traced, tx is not what is sent, and with -c 1 the library generates
+   every expected payload on the CPU */
+static int validate_hostlink_seq(const mpxh_options *o, FILE *err)
+{
+    const int top = o->sweep_min > 0 ? o->sweep_max : o->buff_sz;
+    if (o->hostlink_seq != 1) {
+        fprintf(err, "invalid -K: its value is 0 or 1\n");
+        return 1;
+    }
+    if (!o->hostlink) {
+        fprintf(err, "invalid -K 1 without -H 1|2: sequenced host-link payloads are a host-link run's (-c 3 is the pair loops')\n");
+        return 1;
+    }
+    if (o->duplex) {
+        fprintf(err, "invalid -K 1 with -X 1: the full-duplex loop keeps sends in flight and stays unsequenced\n");
+        return 1;
+    }
+    if (o->hostlink_lat_cap >= 0) {
+        fprintf(err, "invalid -K 1 with -T %d: sequenced host-link calls are never traced by the host-link recorder\n",
+                o->hostlink_lat_cap);
+        return 1;
+    }
+    if (o->check == 2 || o->check == 3) {
+        fprintf(err, "invalid -K 1 with -c %d: a sequenced host-link call does not send tx; -c 0|1\n", o->check);
+        return 1;
+    }
+    if (o->check == 1 && o->iters > 0 && top > 0 && (unsigned long long)o->iters * (unsigned long long)top > MPXH_SEQ_AUTO_MAX) {
+        fprintf(err, "invalid -K 1 -c 1 with -i %d and -b %d: more than %llu bytes of expected payloads to generate per run\n",
+                o->iters, top, MPXH_SEQ_AUTO_MAX);
+        return 1;
+    }
+    return 0;
+}
+
 int mpxh_validate(const mpxh_options *o, int world, FILE *err)
 {
     if (o->check == 3 && validate_seq(o, err)) return 1;
     if (o->fan_seq && validate_fan_seq(o, world, err)) return 1;
+    if (o->hostlink_seq && validate_hostlink_seq(o, err)) return 1;
     /* -T (the host-link recorder): a -H run of the blocking loops */
     if (o->hostlink_lat_cap >= 0 && !o->hostlink) {
         fprintf(err, "invalid -T %d without -H: the host-link recorder traces host-link calls only\n", o->hostlink_lat_cap);

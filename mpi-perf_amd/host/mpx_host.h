@@ -75,6 +75,11 @@ typedef struct mpxh_options {
                                            sequenced fan call (mpx_xfer_fan_seq):
                                            a payload per (src, dst, iteration);
                                            a malformed value reads as -1      */
+    int hostlink_seq;               /* -K  1: with -H 1|2 (not -X 1), every run
+                                           is a sequenced host-link call on both
+                                           ends (mpx_xfer_hostlink_seq /
+                                           mpx_host_xfer_seq); a malformed value
+                                           reads as -1                        */
 } mpxh_options;
 
 /* parse status */
@@ -91,7 +96,7 @@ enum {
 /* defaults of main(), mpi_perf.c:388-392 (+ the new fields) */
 void mpxh_defaults(mpxh_options *o);
 /* parse_args, mpi_perf.c:273-339 (getopt ":f:n:d:p:i:b:u:h:r:l:x:" plus
-   "w:e:a:c:S:t:g:A:L:m:P:H:X:T:Q:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
+   "w:e:a:c:S:t:g:A:L:m:P:H:X:T:Q:K:"); fills o->uuid with a fresh v4 UUID.  Resets getopt. */
 int mpxh_parse_args(mpxh_options *o, int argc, char **argv);
 /* print_usage, mpi_perf.c:20-32 (the reference's text, then the new flags) */
 void mpxh_print_usage(FILE *f);
@@ -129,7 +134,8 @@ int mpxh_fan_peers(int world, int rank, int *peers);
    MPXH_SEQ_AUTO_MAX; -Q against a value other than 0 or 1, a run without
    -m, -c 2, -P and, with -c 1, (world - 1) x -i x -b above
    MPXH_SEQ_AUTO_MAX (-c 3 with -m keeps its own refusal, which comes
-   first); then group_size, mpi_perf.c:399-403 (with -H the
+   first); -K against a value other than 0 or 1, a run without -H, -X 1,
+   -T, -c 2|3 and, with -c 1, -i x -b above MPXH_SEQ_AUTO_MAX; then group_size, mpi_perf.c:399-403 (with -H the
    job is the 2 * world ranks: the GPU ranks and their endpoints).
    Returns:
    0 ok, 1 invalid (message printed, caller aborts), 2 the reference divides

@@ -34,7 +34,9 @@
  * those 2 * w ranks, the GPU ranks group 1 (-H 1) or group 0 (-H 2).  With
  * -X 1 beside -H every run is the full-duplex non-blocking loop on that link
  * (mpx_xfer_hostlink_duplex / mpx_host_xfer_duplex); -H still says which side
- * is group 1 in the records.
+ * is group 1 in the records.  With -K 1 beside -H (not -X 1) every run is a
+ * sequenced host-link call on both ends (mpx_xfer_hostlink_seq /
+ * mpx_host_xfer_seq: a generated payload per iteration; -c 0|1).
  *
  * Built with -DMPX_WINDOWS_CLI (bin/mpx_perf_win), the front end is the
  * Windows / MS-MPI variant's (/root/reference/windows/mpi-perf.cpp):
@@ -420,7 +422,10 @@ static void *rank_main(void *arg)
             /* -c 3: every run is a sequenced call (mpx_xfer_seq): the library
                generates the expected payloads itself, from the run's seed */
             const int seq = opt.check == 3 && !opt.use_dotnet;
-            if (opt.check && !opt.use_dotnet && !seq) {
+            /* -H -K 1: every run is a sequenced host-link call on both ends;
+               -c 1 checks every payload against the library's expectations */
+            const int hseq = opt.hostlink_seq == 1 && !opt.use_dotnet;
+            if (opt.check && !opt.use_dotnet && !seq && !hseq) {
                 /* expected payloads: the peer's tx, read after every fill */
                 uint64_t s, s1;
                 checksum_tx(r, (size_t)B, &s);
@@ -456,6 +461,14 @@ static void *rank_main(void *arg)
             } else if (opt.duplex) { /* -H -X 1: the full-duplex loop, both sides alike */
                 if (is_endpoint(r)) MPX_CHECK(mpx_host_xfer_duplex(ctx, r, peer, opt.iters, B, &xo, &tm));
                 else MPX_CHECK(mpx_xfer_hostlink_duplex(ctx, r, peer, opt.iters, tx_of[r], rx_of[r], B, &xo, &tm));
+            } else if (hseq) { /* the seed is derived as -c 3 derives it: the same on both ends */
+                mpx_seq_opts so;
+                memset(&so, 0, sizeof so);
+                so.seed = MPXH_SEQ_RUN_SEED(MPX_PATTERN_SEED, run_idx);
+                so.check = opt.check == 1;
+                so.timeout_ms = (uint32_t)opt.timeout_ms;
+                if (is_endpoint(r)) MPX_CHECK(mpx_host_xfer_seq(ctx, xfer_mode(), group, r, peer, opt.iters, B, &so, &tm));
+                else MPX_CHECK(mpx_xfer_hostlink_seq(ctx, xfer_mode(), group, r, peer, opt.iters, tx_of[r], rx_of[r], B, &so, &tm));
             } else if (is_endpoint(r)) { /* -H: the endpoint's side, on this thread */
                 MPX_CHECK(mpx_host_xfer(ctx, xfer_mode(), group, r, peer, opt.iters, B, &xo, &tm));
             } else if (opt.hostlink) {

@@ -285,6 +285,10 @@ _SIGS = {
     "mpx_seq_expect": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint64)]),
     "mpx_xfer_fan_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_size_t, C.POINTER(FanSeqOpts), C.POINTER(Timing), C.POINTER(FanLink)]),
+    "mpx_xfer_hostlink_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.POINTER(SeqOpts), C.POINTER(Timing)]),
+    "mpx_host_xfer_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SeqOpts),
+                                    C.POINTER(Timing)]),
     "mpx_rccl_version": (C.c_int, [C.POINTER(C.c_int), C.c_char_p, C.c_int]),
     "mpx_rccl_get_unique_id": (C.c_int, [C.c_void_p]),
     "mpx_rccl_init_rank": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -614,6 +618,52 @@ class Context:
         st = self.L.mpx_host_xfer(self.h, mode, group, host_rank, peer_rank, iters, length, C.byref(o), C.byref(t))
         if st != OK:
             e = MpxError(st, "mpx_host_xfer")
+            e.timing = t
+            raise e
+        return t
+
+    # host link, sequenced payloads (include/mpx_hostlink_seq.h)
+    @staticmethod
+    def _seq_opts(seed, check_payload, expect, timeout_ms, nwg, flags=0):
+        arr = None
+        if expect is not None:
+            expect = list(expect)
+            arr = (C.c_uint64 * max(len(expect), 1))(*expect)
+        o = SeqOpts(seed=seed & 0xFFFFFFFFFFFFFFFF, check=1 if check_payload else 0, flags=flags, timeout_ms=timeout_ms,
+                    nwg=nwg, expect=C.cast(arr, C.POINTER(C.c_uint64)) if arr is not None else None)
+        return o, arr   # (arr: kept alive by the caller for the call)
+
+    def xfer_hostlink_seq(self, mode: int, group: int, my_rank: int, host_rank: int, iters: int, tx: Buffer, rx: Buffer,
+                          length: int, seed: int, check_payload: bool = False, expect=None, timeout_ms: int = 0,
+                          nwg: int = 0, flags: int = 0) -> Timing:
+        """mpx_xfer_hostlink_seq: GPU rank my_rank's side of the host-link loop
+        with a generated payload of its own in every iteration.  expect: check
+        mode, the checksum of each of the `iters` payloads this side receives
+        (None: the library computes them).  A failing call raises MpxError
+        carrying .timing"""
+        o, keep = self._seq_opts(seed, check_payload, expect, timeout_ms, nwg, flags)
+        t = Timing()
+        st = self.L.mpx_xfer_hostlink_seq(self.h, mode, group, my_rank, host_rank, iters, C.c_void_p(tx.ptr),
+                                          C.c_void_p(rx.ptr), length, C.byref(o), C.byref(t))
+        del keep
+        if st != OK:
+            e = MpxError(st, "mpx_xfer_hostlink_seq")
+            e.timing = t
+            raise e
+        return t
+
+    def host_xfer_seq(self, mode: int, group: int, host_rank: int, peer_rank: int, iters: int, length: int, seed: int,
+                      check_payload: bool = False, expect=None, timeout_ms: int = 0, nwg: int = 0,
+                      flags: int = 0) -> Timing:
+        """mpx_host_xfer_seq: host endpoint host_rank's side of the same loop,
+        on the calling thread; a bulk send writes each payload into the
+        endpoint's tx"""
+        o, keep = self._seq_opts(seed, check_payload, expect, timeout_ms, nwg, flags)
+        t = Timing()
+        st = self.L.mpx_host_xfer_seq(self.h, mode, group, host_rank, peer_rank, iters, length, C.byref(o), C.byref(t))
+        del keep
+        if st != OK:
+            e = MpxError(st, "mpx_host_xfer_seq")
             e.timing = t
             raise e
         return t

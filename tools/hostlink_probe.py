@@ -68,6 +68,21 @@ its lines to profiles/hostlink_lat.jsonl (--out), all from one process:
     numa              as above.
 
     python tools/hostlink_probe.py --lat
+
+--seq measures what a sequenced call costs (include/mpx_hostlink_seq.h) and
+APPENDS its lines to profiles/hostlink_seq.jsonl (--out), all from one process:
+
+    seq_cost          the sequenced call beside the ordinary call of the same
+                      shape, interleaved rounds in one job: the 8 B ping-pong
+                      half round trip in both orientations (5 x 2000
+                      iterations) and 4 MiB unidir in each direction (5 x 50),
+                      on the kernel's clock.  The host-to-device bulk figure
+                      includes the endpoint's CPU writing every payload into
+                      its tx before it announces it; the CPU's generation rate
+                      alone is tools/hostlink_seq_host_check's `rate` line.
+    numa              as above.
+
+    python tools/hostlink_probe.py --seq
 """
 import argparse
 import ctypes as C
@@ -84,13 +99,14 @@ ap.add_argument("--bw-bytes", type=int, default=4 << 20)
 ap.add_argument("--bw-iters", type=int, default=50)
 ap.add_argument("--duplex", action="store_true", help="measure the full-duplex loop; appends to --out")
 ap.add_argument("--lat", action="store_true", help="measure the host-link recorder; appends to --out")
+ap.add_argument("--seq", action="store_true", help="measure the sequenced calls beside the ordinary ones; appends to --out")
 ap.add_argument("--lat-off-only", action="store_true", help="with --lat: the tracing-off figures only")
 ap.add_argument("--lat-iters", type=int, default=100000)
 ap.add_argument("--out", default=None, help="default: profiles/hostlink_duplex.jsonl, with --lat profiles/hostlink_lat.jsonl")
 args = ap.parse_args()
 if args.out is None:
     args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                            "hostlink_lat.jsonl" if args.lat else "hostlink_duplex.jsonl")
+                            "hostlink_seq.jsonl" if args.seq else "hostlink_lat.jsonl" if args.lat else "hostlink_duplex.jsonl")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-perf_amd"))
 import mpx  # noqa: E402
 
@@ -120,8 +136,9 @@ for k in range(0, CAP, 4096):
 cpu_of = {}
 
 
-def call(mode, gpu_group, n, iters, nwg=0):
-    """one call, both sides; (the GPU side's loop seconds on the kernel's clock, its Timing, the endpoint's)"""
+def call(mode, gpu_group, n, iters, nwg=0, seed=None):
+    """one call, both sides; (the GPU side's loop seconds on the kernel's clock, its Timing, the endpoint's).
+    seed: both sides make the sequenced call under that seed"""
     out, errs = {}, []
     bar = threading.Barrier(2)
 
@@ -129,7 +146,11 @@ def call(mode, gpu_group, n, iters, nwg=0):
         try:
             cpu_of[r] = libc.sched_getcpu()
             bar.wait()
-            if r == G:
+            if seed is not None and r == G:
+                out[r] = c.xfer_hostlink_seq(mode, gpu_group, G, E, iters, gtx, grx, n, seed, timeout_ms=20000, nwg=nwg)
+            elif seed is not None:
+                out[r] = c.host_xfer_seq(mode, 1 - gpu_group, E, G, iters, n, seed, timeout_ms=20000, nwg=nwg)
+            elif r == G:
                 out[r] = c.xfer_hostlink(mode, gpu_group, G, E, iters, gtx, grx, n, timeout_ms=20000, nwg=nwg)
             else:
                 out[r] = c.host_xfer(mode, 1 - gpu_group, E, G, iters, n, timeout_ms=20000, nwg=nwg)
@@ -367,6 +388,51 @@ def lat_probe():
     return lines
 
 
+# ---- sequenced calls beside ordinary ones (--seq) -----------------------------------
+def seq_probe():
+    B, IT = args.bw_bytes, args.bw_iters
+    lines = []
+    clock = "kernel (s_memrealtime), posted wait excluded"
+
+    def emit(**kw):
+        lines.append(json.dumps(dict(kind=KIND, **kw)))
+        print(lines[-1], flush=True)
+
+    shapes = (("8 B ping-pong half round trip", mpx.MODE_PINGPONG, 1, 8, 2000, "half_rtt_us"),
+              ("8 B ping-pong half round trip", mpx.MODE_PINGPONG, 0, 8, 2000, "half_rtt_us"),
+              ("4 MiB unidir, device to host", mpx.MODE_UNIDIR, 1, B, IT, "GBps"),
+              ("4 MiB unidir, host to device (the endpoint writes every payload into tx)", mpx.MODE_UNIDIR, 0, B, IT, "GBps"))
+    for what, mode, gpu_group, n, iters, unit in shapes:
+        per = {"ordinary": [], "sequenced": []}
+        call(mode, gpu_group, n, iters)
+        call(mode, gpu_group, n, iters, seed=1)
+        for k in range(args.calls):
+            per["ordinary"].append(call(mode, gpu_group, n, iters)[0])
+            per["sequenced"].append(call(mode, gpu_group, n, iters, seed=100 + k)[0])
+        if unit == "GBps":
+            fig = {name: spread([n * iters / x / 1e9 for x in v], 1, 2) for name, v in per.items()}
+        else:
+            fig = {name: spread([x / iters / 2 for x in v], 1e6) for name, v in per.items()}
+        emit(item="seq_cost", what=what, gpu_group=gpu_group, bytes=n, iters=iters, rounds=args.calls, unit=unit, **fig,
+             sequenced_over_ordinary=round(fig["sequenced"]["median"] / fig["ordinary"]["median"], 3), clock=clock)
+    try:
+        gpu_node = int(open(f"/sys/bus/pci/devices/{mpx.bus_id(0).lower()}/numa_node").read())
+    except OSError:
+        gpu_node = None
+    emit(item="numa", binding="not controlled: no thread or allocation was bound to a node", gpu_numa_node=gpu_node,
+         endpoint_tx_node=node_of_page(C.addressof(htx)), endpoint_rx_node=node_of_page(C.addressof(hrx)),
+         gpu_side_thread=dict(cpu=cpu_of.get(G), node=node_of_cpu(cpu_of.get(G, -1))),
+         endpoint_thread=dict(cpu=cpu_of.get(E), node=node_of_cpu(cpu_of.get(E, -1))))
+    return lines
+
+
+if args.seq:
+    out_lines = seq_probe()
+    c.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write("\n".join(out_lines) + "\n")
+    sys.exit(0)
 if args.duplex:
     duplex_probe()
     c.close()
